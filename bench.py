@@ -1,15 +1,23 @@
 #!/usr/bin/env python3
 """bench.py -- training images/sec of PackNet-SAN + depth-edge loss at 384x1280, bf16 compute, on N MI355X.
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 One "step" = zero_grad + forward (dropout 0.5, random whole-batch flip) + silog/edge loss + backward + bucketed RCCL
 gradient all-reduce (N > 1) + fused Adam, on a synthetic batch of 8 frames per GPU that is already resident in HBM
-(SURVEY.md 8(d) recipe).  Rank 0 prints ONE JSON line.  Extra objects: "roofline" for the dominant kernel family
-(MFMA implicit-GEMM convolutions; algorithmic FLOPs / HIP-event time of every launch), "roofline_hbm": the same for the
-HBM-bound GroupNorm+ELU family (algorithmic bytes / HIP-event time against 8 TB/s), and, at N = 1,
-"cpu_baseline": the CPU oracle (oracle/) timed on this box's host cores on a bounded sample.
+(SURVEY.md 8(d) recipe).  Rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, ...).  The backward pass adds a few
+weight-gradient tails with fp32 atomics, so the parameters drift apart from run to run; the last timed step therefore starts
+from the initial parameters and random-number state (restored in place, as the optimizer writes parameters), and what it
+computes is the same in every run with the same arguments.  --dump-outputs DIR writes that step's outputs (loss terms,
+inverse-depth maps) as DIR/<name>.npy.
+
+--full adds the measurements that take runs of their own: "roofline" for the dominant kernel family (MFMA implicit-GEMM
+convolutions; algorithmic FLOPs / HIP-event time of every launch), "roofline_hbm": the same for the HBM-bound GroupNorm+ELU family (algorithmic bytes / HIP-event time against 8 TB/s), the host's enqueue cost of unthrottled
+steps, and, at N = 1, the all-reduce layout, "cpu_baseline": the CPU oracle (oracle/) timed on this box's host cores on a
+bounded sample, and "parity" against that oracle.
 """
 import argparse
 import json
@@ -45,8 +53,53 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timing", action="store_true")
     ap.add_argument("--cpu-steps", type=int, default=2)
-    ap.add_argument("--dump-conv", type=str, default="", help="write per-launch conv timings (shape, ms, TFLOP/s) to this file")
-    return ap.parse_args()
+    ap.add_argument("--dump-conv", type=str, default="", help="write per-launch conv timings (shape, ms, TFLOP/s) to this file (--full)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="write what the last timed step computed as DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the per-kernel timing, unthrottled host-enqueue steps, all-reduce layout, CPU baseline and parity check")
+    args = ap.parse_args()
+    if args.dump_conv and not (args.full and not args.no_kernel_timing):
+        ap.error("--dump-conv needs the per-kernel timing of --full")
+    return args
+
+
+DUMP_BUDGET_ELEMS = 60 * 2**20 // 4                # --dump-outputs: float32 elements in all (under 64 MB with the .npy headers)
+
+
+def _output_arrays(out, prefix=""):
+    """name -> tensor for every tensor in a step's output (nested dicts / lists flattened: inv_depths_0, metrics_edge_loss, ...)"""
+    items = out.items() if isinstance(out, dict) else enumerate(out) if isinstance(out, (list, tuple)) else ()
+    res = {}
+    for k, v in items:
+        name = "%s%s" % (prefix, k)
+        if torch.is_tensor(v):
+            res[name] = v
+        elif isinstance(v, (dict, list, tuple)):
+            res.update(_output_arrays(v, name + "_"))
+    return res
+
+
+def snapshot_outputs(out):
+    """Host copies (float32) of the step's outputs, right after the timed steps: later work (the --full passes) runs more
+    steps and may reuse the device buffers."""
+    return {k: v.detach().float().cpu().numpy().reshape(v.shape) for k, v in _output_arrays(out).items()}
+
+
+def dump_outputs(arrays, path):
+    """Writes each array as path/<name>.npy.  Arrays are kept whole while they fit the 64 MB budget; what does not fit is
+    reduced to a fixed sample (seeded, the same element indices on every run of the same arguments), stored 1-D."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    left, names = DUMP_BUDGET_ELEMS, sorted(arrays, key=lambda k: (arrays[k].size, k))
+    for i, name in enumerate(names):
+        a = np.asarray(arrays[name], dtype=np.float32)
+        cap = left // (len(names) - i)
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(20240611).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        left -= a.size
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 class ConvTimer:
@@ -345,16 +398,35 @@ def main():
     torch.manual_seed(1000 + rank)                       # decorrelated per-rank dropout masks
 
     timer = None
-    if not args.no_kernel_timing:
+    if args.full and not args.no_kernel_timing:
         timer = ConvTimer(K)
         timer.install()
 
+    kept = {}                          # the output dict of the last timed step (--dump-outputs)
+    restore_start = None
     if args.mode == "train":
         model.train()
         flat = FlatParameters(net.parameters())
         broadcast_parameters(flat)
         reducer = BucketedAllReduce(flat, force=True) if dist_on else None
         opt = FusedAdam(flat, lr=1e-4, reducer=reducer)
+        start = {"params": flat.flat.clone(), "cuda_rng": torch.cuda.get_rng_state(dev), "cpu_rng": torch.get_rng_state(),
+                 "py_rng": random.getstate()}
+
+        def restore_start():
+            """The initial parameters and random-number state (dropout masks, flip draw) back in place for the last timed step.
+            Ordered like the optimizer's own parameter write: after the side streams' work (the weight packs being rebuilt from
+            the previous parameters), then the packs are invalidated and rebuilt."""
+            for st in K._side["streams"]:
+                ev = torch.cuda.Event()
+                ev.record(st)
+                torch.cuda.current_stream().wait_event(ev)
+            flat.flat.copy_(start["params"])
+            K.bump_weights_epoch()
+            K.prefetch_weight_packs()
+            torch.cuda.set_rng_state(start["cuda_rng"], dev)
+            torch.set_rng_state(start["cpu_rng"])
+            random.setstate(start["py_rng"])
 
         boundary = []                      # MTE_BENCH_BOUNDARY=1 (development): GPU time from the end of Adam to the first kernel of the next forward
         if os.environ.get("MTE_BENCH_BOUNDARY"):
@@ -372,7 +444,7 @@ def main():
             import mindtheedge_amd.networks.layers.packnet.layers01 as _l01
             _l01.K = K
 
-        def eager_step():
+        def eager_step(keep=False):
             opt.zero_grad()
             out = model(batch)
             out["loss"].backward()
@@ -380,6 +452,8 @@ def main():
             if os.environ.get("MTE_BENCH_BOUNDARY"):
                 state["adam"] = torch.cuda.Event(enable_timing=True)
                 state["adam"].record()
+            if keep:
+                kept["out"] = out
             return out["loss"]
         step, launch_mode = eager_step, "eager"
         if dist_on:
@@ -395,7 +469,12 @@ def main():
             from mindtheedge_amd.utils.graph import GraphedTrainStep
             graphed = GraphedTrainStep(model, opt, batch)
             if graphed.graphed:
-                step, launch_mode = (lambda: graphed()["loss"]), "hip_graph"
+                def graph_step(keep=False):
+                    out = graphed()
+                    if keep:
+                        kept["out"] = out
+                    return out["loss"]
+                step, launch_mode = graph_step, "hip_graph"
             else:
                 launch_mode = "eager (capture failed: %s)" % graphed.error
                 print("bench.py: HIP-graph capture of the training step failed, running eagerly: %s" % graphed.error, file=sys.stderr)
@@ -404,9 +483,12 @@ def main():
         eager_step = None
         model.eval()
 
-        def step():
+        def step(keep=False):
             with torch.no_grad():
-                return model(batch)["inv_depths"][0][0]
+                out = model(batch)
+            if keep:
+                kept["out"] = out
+            return out["inv_depths"][0][0]
 
     def sync():
         if dist_on:
@@ -417,20 +499,26 @@ def main():
         last = step()
     sync()
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        last = step()
+    for i in range(args.steps):
+        if i == args.steps - 1 and restore_start is not None:
+            restore_start()
+        last = step(keep=i == args.steps - 1)
     host_dt = time.perf_counter() - t0                   # time the host needed to ENQUEUE the steps (it runs ahead of the GPU)
     torch.cuda.synchronize()
     dt_local = time.perf_counter() - t0                  # this rank's own steps done (before the barrier): straggler spread across ranks
     sync()
     dt = time.perf_counter() - t0
-    # the host's own cost per step: three steps enqueued right after a sync (empty queues: `host_dt` above also contains the time the
-    # host spends blocked on full hardware queues while it runs ahead of the GPU)
-    t1 = time.perf_counter()
-    for _ in range(3):
-        last = step()
-    host_free_dt = (time.perf_counter() - t1) / 3
-    sync()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(snapshot_outputs(kept.pop("out")), args.dump_outputs)
+    host_free_dt = None
+    if args.full:
+        # the host's own cost per step: three steps enqueued right after a sync (empty queues: `host_dt` above also contains the time the
+        # host spends blocked on full hardware queues while it runs ahead of the GPU)
+        t1 = time.perf_counter()
+        for _ in range(3):
+            last = step()
+        host_free_dt = (time.perf_counter() - t1) / 3
+        sync()
     if args.mode == "train" and boundary:
         gaps = [a.elapsed_time(b) for a, b in boundary[-args.steps + 1:]]
         print("step boundary (end of Adam -> image conversion of the next step), ms: min %.3f median %.3f max %.3f"
@@ -487,11 +575,13 @@ def main():
                           "global_batch": B * world, "height": H, "width": W,
                           "parallelism": "dp%d (bucketed RCCL all-reduce overlapped with backward)" % world if world > 1 else "single GPU"},
                "final_loss" if args.mode == "train" else "mean_inv_depth": final,
-               "host_enqueue_ms_per_step": host_dt / args.steps * 1e3, "host_enqueue_unthrottled_ms_per_step": host_free_dt * 1e3,
+               "host_enqueue_ms_per_step": host_dt / args.steps * 1e3,
                "step_launch": launch_mode,
                # fastest / slowest rank's own ms per step, measured to its local device sync BEFORE the closing barrier: the spread
                # is straggler time, to be read beside allreduce.allreduce_exposed_ms (both are inside ms_per_step)
                "rank_ms_per_step_min": rank_ms[0], "rank_ms_per_step_max": rank_ms[1]}
+        if host_free_dt is not None:
+            res["host_enqueue_unthrottled_ms_per_step"] = host_free_dt * 1e3
         passes = 3.0 if args.mode == "train" else 1.0
         step_flops = conv_flops_per_image(H, W) * B * passes
         res["mfma_fraction_of_step"] = step_flops / (ms * 1e-3) / (BF16_DENSE_PEAK_TFLOPS * 1e12)
@@ -545,15 +635,15 @@ def main():
         if args.mode == "train":
             # data-parallel readiness (spec horovod_trainer.py:53-55): the bucket / message layout the gradient
             # all-reduce uses, the order the buckets were launched in during the last backward and the device time the step
-            # waited for RCCL in finish() -- at N = 1 the layout of the same network is reported without a collective
+            # waited for RCCL in finish() -- at N = 1 (--full) the layout of the same network is reported without a collective
             if reducer is not None:
                 res["allreduce"] = {"rccl_ranks": dist.get_world_size(), "backend": dist.get_backend(), **reducer.describe(),
                                     "allreduce_exposed_ms": reducer.exposed_ms(), "gradient_mb": round(flat.total * 4 / 2**20, 1)}
-            else:
+            elif args.full:
                 layout = BucketedAllReduce(flat)
                 res["allreduce"] = {"rccl_ranks": 1, "backend": None, **layout.describe(), "allreduce_exposed_ms": 0.0,
                                     "gradient_mb": round(flat.total * 4 / 2**20, 1)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(H, W, args.cpu_steps)
             try:
                 res["parity"] = parity_check(net, K, H, W)

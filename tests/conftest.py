@@ -16,12 +16,16 @@ def pytest_configure(config):
 
 
 def load_golden(name):
+    """<name>.npz, merged with <name>.part2.npz where a fixture was split to keep every committed file under 1 MiB."""
     import torch
-    z = np.load(os.path.join(GOLDEN, name + ".npz"), allow_pickle=False)
     out = {}
-    for k in z.files:
-        a = z[k]
-        out[k] = a if a.dtype.kind in "US" else torch.from_numpy(a)
+    for path in (os.path.join(GOLDEN, name + ".npz"), os.path.join(GOLDEN, name + ".part2.npz")):
+        if path.endswith(".part2.npz") and not os.path.exists(path):
+            continue
+        z = np.load(path, allow_pickle=False)
+        for k in z.files:
+            a = z[k]
+            out[k] = a if a.dtype.kind in "US" else torch.from_numpy(a)
     return out
 
 

@@ -12,8 +12,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.mark.timeout(600)
 def test_bench_json_contract():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline"],
-                       capture_output=True, text=True, timeout=580, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
+                        "--full"], capture_output=True, text=True, timeout=580, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -40,6 +40,39 @@ def test_bench_json_contract():
     assert max(ar["messages_per_bucket"]) >= 5                                   # ... which goes out as <= 32 MB messages
     # round 3: per-rank step time (fastest / slowest rank, before the closing barrier) beside the max-over-ranks figure
     assert 0 < d["rank_ms_per_step_min"] <= d["rank_ms_per_step_max"] <= d["ms_per_step"] * 1.001
+
+
+@pytest.mark.timeout(900)
+def test_plain_run_is_lean_and_dumps_the_last_timed_step(tmp_path):
+    """Without --full the run only times its steps: no per-kernel timing, CPU baseline or extra steps.  --dump-outputs writes
+    what the last timed step computed (float32 .npy files, at most 64 MB in all); its loss is the one the line reports, and two
+    runs with the same arguments write the same arrays."""
+    import numpy as np
+    runs = []
+    for tag in ("a", "b"):
+        out = tmp_path / tag
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--dump-outputs", str(out)],
+                           capture_output=True, text=True, timeout=400, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        runs.append((json.loads(lines[0]), out))
+    d, out = runs[0]
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "bf16" and d["higher_is_better"] is True
+    assert abs(d["value"] - 8 * 1000.0 / d["ms_per_step"]) < 1e-6 * d["value"]
+    for k in ("roofline", "roofline_hbm", "cpu_baseline", "parity", "host_enqueue_unthrottled_ms_per_step"):
+        assert k not in d, k
+    files = sorted(p.name for p in out.iterdir())
+    assert {"loss.npy", "inv_depths_0.npy", "inv_depths_3.npy"} <= set(files), files
+    assert sum(p.stat().st_size for p in out.iterdir()) <= 64 * 2**20
+    arrays = {f[:-4]: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["inv_depths_0"].shape == (8, 1, 384, 1280)
+    assert abs(float(arrays["loss"].sum()) - d["final_loss"]) <= 1e-6 * abs(d["final_loss"])
+    d2, out2 = runs[1]
+    assert sorted(p.name for p in out2.iterdir()) == files and d2["final_loss"] == d["final_loss"]
+    for f in files:
+        assert np.array_equal(np.load(out2 / f), arrays[f[:-4]]), f
 
 
 @pytest.mark.timeout(900)

@@ -269,7 +269,7 @@ def test_a_cluster_wait_that_gives_up_is_reported_not_silent():
 
 
 @pytest.mark.parametrize("hog_wgs", [192, 256, 384])
-def test_cluster_kernels_beside_a_kernel_that_holds_the_compute_units(hog_wgs):
+def test_cluster_kernels_beside_a_kernel_that_holds_the_compute_units(hog_wgs, tmp_path):
     """advisor (round 4): "add a test that runs the cluster kernels under a CU-hogging kernel on another stream".  tools/probe/cu_hog.hip (512 threads,
     96 KB LDS, the whole register file of its SIMDs: nothing shares a CU with it, matrix cores busy) holds 192 / 256 / 384 workgroup slots of the chip for a
     few milliseconds on a side stream while the GroupNorm cluster kernels (forward and backward, 512 channels at 24x80, B = 8: clusters of workgroups that
@@ -285,7 +285,7 @@ def test_cluster_kernels_beside_a_kernel_that_holds_the_compute_units(hog_wgs):
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools", "probe", "cu_hog.hip")
     if not os.path.exists(hipcc):
         pytest.skip("no hipcc on this box")
-    so = "/tmp/libcu_hog_test.so"
+    so = str(tmp_path / "libcu_hog_test.so")
     subprocess.check_call([hipcc, "--offload-arch=gfx950", "-O3", "-shared", "-fPIC", "-o", so, src])
     hog = ctypes.CDLL(so)
     hog.hog_launch.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int]

@@ -5,10 +5,10 @@ mkdir -p gpurun_out
 for rep in $(seq $reps); do
   for lib in "" "$other"; do
     export MTE_LIB_PATH=$lib
-    python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1 > gpurun_out/ab_lib_$rep.json
-    python - "${lib:-in-tree}" gpurun_out/ab_lib_$rep.json <<'PY'
+    line=$(python bench.py --steps 20 --warmup 5 --no-cpu-baseline --full 2>/dev/null | tail -1)
+    python - "${lib:-in-tree}" "$line" <<'PY'
 import json, sys
-d = json.loads(open(sys.argv[2]).read().strip().splitlines()[-1])
+d = json.loads(sys.argv[2])
 r, h = d.get("roofline", {}), d.get("roofline_hbm", {})
 bk = r.get("by_kernel", {})
 print("%-22s %7.2f img/s %6.2f ms/step  conv %6.2f ms (frac %.3f)  igemm %5.2f ms" % (sys.argv[1][-22:], d["value"], d["ms_per_step"],

@@ -1,9 +1,10 @@
 #!/bin/bash
 # development aid: which kernels sit before / after the __amd_rocclr_copyBuffer launches of a training step (who issues the device copies?)
+root=$(cd "$(dirname "$0")/.." && pwd)
 out=$GRAFT_REPO_ROOT/gpurun_out
 mkdir -p $out; rm -rf /tmp/trC
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d /tmp/trC -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing > $out/copy_trace_run.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $TMPDIR/trC -- python3 $root/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-kernel-timing --full > $out/copy_trace_run.txt 2>&1
 cd $GRAFT_REPO_ROOT
 python3 - "$(find /tmp/trC -name '*kernel_trace.csv' | head -1)" <<'PY'
 import csv, sys, collections

@@ -22,5 +22,5 @@ cp "$(find /tmp/trS -name '*kernel_stats.csv' | head -1)" $out/r02_${tag}_train_
 python tools/trace_summary.py "$(find /tmp/trO -name '*kernel_trace.csv' | head -1)" 4 90 > $out/r02_${tag}_train_T8_trace_summary.txt
 python tools/trace_summary.py "$(find /tmp/trS -name '*kernel_trace.csv' | head -1)" 4 60 > $out/r02_${tag}_train_T8_serial_trace_summary.txt
 python3 tools/pmc_traffic.py /tmp/pmcF /tmp/pmcW 3 > $out/r02_${tag}_pmc_traffic_T8.txt
-python bench.py --steps 20 --warmup 5 --dump-conv $out/r02_${tag}_conv_table.txt > $out/r02_${tag}_train_T8_bench.json 2> $out/r02_${tag}_bench.err
+python bench.py --steps 20 --warmup 5 --full --dump-conv $out/r02_${tag}_conv_table.txt > $out/r02_${tag}_train_T8_bench.json 2> $out/r02_${tag}_bench.err
 head -3 $out/r02_${tag}_train_T8_serial_trace_summary.txt; tail -c 600 $out/r02_${tag}_train_T8_bench.json
