@@ -302,6 +302,22 @@ int mte_edge_loss_finalize(const double* sums, int B, long numel, float weight, 
 int mte_edge_loss_bwd(const float* pred, const float* edge, const float* normal, const float* mask, const float* coef, const float* gout,
                       float* dpred, int B, int H, int W, int from_inv, int is_grad, int is_sigmoid, float thresh, mte_stream_t stream);
 
+/* ---- the other edge-loss choices of GradLoss (losses/grad_loss.py:139-156), one scale per launch:
+ *      kind 0 'cross_entropy' (comp_cross_entropy, grad_loss.py:161-219), kind 1 'attention_loss' (attention_loss2 with one alpha for the
+ *      batch, losses/attention_loss.py:21-49), kind 2 'spatially_adaptive' (attention_loss2 with the per-pixel 15x15 box alpha,
+ *      attention_loss.py:27-31); dice != 0 adds the dice term of grad_loss.py:151-156.  loss = weight * (base + dice).
+ *   maps fp32 [B,H,W]; normal / mask / gmap nullable; from_inv / is_grad / is_sigmoid / thresh as mte_edge_loss_fwd
+ *   work : mte_edge_loss_kind_work_elems(B, H, W) doubles (content on entry ignored: each forward launch clears what it needs)
+ *   fwd  : loss[1] <- the loss scalar; coef [2B + 5] <- backward coefficients (computed on the device by the last workgroup; no host sync)
+ *   bwd  : dpred <- gout * d loss / d pred (gout: device scalar, nullable = 1) */
+long mte_edge_loss_kind_work_elems(int B, int H, int W);   /* attention_loss.py:21-49 / grad_loss.py:139-156: [B][13] sums, tickets, one record per 64x32 tile */
+int mte_edge_loss_kind_fwd(const float* pred, const float* edge, const float* normal, const float* mask, float* gmap, int B, int H, int W,
+                           int kind, int dice, int from_inv, int is_grad, int is_sigmoid, float thresh, float weight, float pos_to_neg,
+                           double* work, float* loss, float* coef, mte_stream_t stream);    /* grad_loss.py:122-156, attention_loss.py:21-49 */
+int mte_edge_loss_kind_bwd(const float* pred, const float* edge, const float* normal, const float* mask, const float* coef, const float* gout,
+                           float* dpred, int B, int H, int W, int kind, int dice, int from_inv, int is_grad, int is_sigmoid, float thresh,
+                           mte_stream_t stream);                                          /* autograd of grad_loss.py:122-156 */
+
 /* F.interpolate(pred, size = label size, mode = 'bilinear') of GradLoss.forward (grad_loss.py:127; identity on the multi-scale
  * training path, where every scale is compared at its own resolution) and its adjoint; fp32 [B,h,w] -> [B,H,W] */
 int mte_resize_bilinear_fwd(const float* x, float* y, int B, int h, int w, int H, int W, mte_stream_t stream);

@@ -47,6 +47,46 @@ class EdgeLossFn(torch.autograd.Function):
         return (dpred,) + (None,) * 10
 
 
+class EdgeLossKindFn(torch.autograd.Function):
+    """weight * (base + dice) for the other edge-loss choices of GradLoss.forward (grad_loss.py:139-156): kind 0 class-balanced BCE
+    ('cross_entropy', only reached here with the dice term), 1 attention_loss2 with one alpha for the batch ('attention_loss'),
+    2 attention_loss2 with the per-pixel 15x15 box alpha ('spatially_adaptive') -- losses/attention_loss.py:21-49; dice adds
+    1000 (sum p^2 + sum t^2 + 1e-4) / (2 sum p t + 1e-4) / N.  One forward and one backward launch, fused with inv2depth when from_inv."""
+
+    @staticmethod
+    def forward(ctx, pred, edge, normal, mask, kind, dice, weight, pos_to_neg, from_inv, is_grad, is_sigmoid, thresh, want_gmap):
+        B, _, H, W = edge.shape
+        pred, edge = pred.contiguous().float(), edge.contiguous().float()
+        normal = None if normal is None else normal.contiguous().float()
+        mask = None if mask is None else mask.contiguous().float()
+        if tuple(pred.shape) != tuple(edge.shape) or (normal is not None and tuple(normal.shape) != tuple(edge.shape)):
+            raise MteError("prediction / label shapes differ: %s vs %s" % (tuple(pred.shape), tuple(edge.shape)))
+        if mask is not None and tuple(mask.shape) != tuple(edge.shape):
+            raise MteError("mask shape %s differs from the label's %s" % (tuple(mask.shape), tuple(edge.shape)))
+        dev = pred.device
+        work = torch.empty((_K.lib.mte_edge_loss_kind_work_elems(B, H, W),), dtype=torch.float64, device=dev)
+        coef = torch.empty((2 * B + 5,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        gmap = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev) if want_gmap else None
+        cfg = (B, H, W, int(kind), int(dice), int(from_inv), int(is_grad), int(is_sigmoid), float(thresh))
+        _K.lib.mte_edge_loss_kind_fwd(pred.data_ptr(), edge.data_ptr(), _K._ptr(normal), _K._ptr(mask), _K._ptr(gmap), *cfg,
+                                      float(weight), float(pos_to_neg), work.data_ptr(), loss.data_ptr(), coef.data_ptr(), _K._stream())
+        ctx.save_for_backward(pred, edge, normal, mask, coef)
+        ctx.cfg = cfg
+        if want_gmap:
+            ctx.mark_non_differentiable(gmap)
+        return loss, gmap
+
+    @staticmethod
+    def backward(ctx, gloss, _g):
+        pred, edge, normal, mask, coef = ctx.saved_tensors
+        dpred = torch.empty_like(pred)
+        gl = gloss.contiguous().float()
+        _K.lib.mte_edge_loss_kind_bwd(pred.data_ptr(), edge.data_ptr(), _K._ptr(normal), _K._ptr(mask), coef.data_ptr(), gl.data_ptr(),
+                                      dpred.data_ptr(), *ctx.cfg, _K._stream())
+        return (dpred,) + (None,) * 12
+
+
 class BilinearResizeFn(torch.autograd.Function):
     """F.interpolate(x, size=(H, W), mode='bilinear') for fp32 [B,1,h,w] maps -- the resize GradLoss.forward applies when the
     prediction and the label differ in size (grad_loss.py:127)."""

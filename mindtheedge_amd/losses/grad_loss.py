@@ -21,14 +21,29 @@ class GradLayer(nn.Module):
         return g, None, None
 
 
+# base losses of grad_loss.py:143-150 in the order the reference tests them (plain substring tests: the LAST one present wins)
+EDGE_LOSS_KINDS = (('cross_entropy', 0), ('attention_loss', 1), ('spatially_adaptive', 2))
+
+
+def parse_edge_loss_type(edge_loss_type):
+    """-> (kind, dice): kind 0 class-balanced BCE, 1 attention_loss2, 2 spatially adaptive attention_loss2; dice adds the dice term
+    ('dice' in the string, grad_loss.py:153).  A string without a base loss fails upstream (UnboundLocalError in forward); here it
+    raises NotImplementedError at construction."""
+    kind = None
+    for name, k in EDGE_LOSS_KINDS:
+        if name in edge_loss_type:
+            kind = k
+    if kind is None:
+        raise NotImplementedError("edge_loss_type %r names no base loss (one of %s)"
+                                  % (edge_loss_type, ", ".join(n for n, _ in EDGE_LOSS_KINDS)))
+    return kind, 'dice' in edge_loss_type
+
+
 class GradLoss(nn.Module):
     def __init__(self, edge_loss_type, use_external_edges_for_loss=True, edge_loss_class_list_to_mask_out=[],
                  depth_edges_loss_weight=1.0, depth_edges_loss_pos_to_neg_weight=1.0):
         super().__init__()
-        if edge_loss_type != 'cross_entropy':
-            # attention_loss / spatially_adaptive / dice exist upstream (grad_loss.py:143-156) but no shipped YAML
-            # selects them; they are outside this build's hot path.
-            raise NotImplementedError("edge_loss_type %r is not built; the shipped configs use 'cross_entropy'" % edge_loss_type)
+        self.loss_kind, self.dice = parse_edge_loss_type(edge_loss_type)
         if len(edge_loss_class_list_to_mask_out) > 0:
             raise NotImplementedError("segmentation-class masking is dead code upstream (list re-set to [] at grad_loss.py:181)")
         self.grad_layer = GradLayer()
@@ -50,7 +65,12 @@ class GradLoss(nn.Module):
                 output = 1.0 / output.clamp(min=1e-6)
                 from_inv_depth = False
             output = K.BilinearResizeFn.apply(output, gt_edge.shape[-2], gt_edge.shape[-1])
-        loss, g = K.EdgeLossFn.apply(output, gt_edge, gt_normals if is_grad else None, gt_mask, self.weight,
-                                     self.depth_edges_loss_pos_to_neg_weight, from_inv_depth, is_grad, is_sigmoid,
-                                     float(sigmoid_thresh), return_grad_map)
+        if self.loss_kind == 0 and not self.dice:
+            loss, g = K.EdgeLossFn.apply(output, gt_edge, gt_normals if is_grad else None, gt_mask, self.weight,
+                                         self.depth_edges_loss_pos_to_neg_weight, from_inv_depth, is_grad, is_sigmoid,
+                                         float(sigmoid_thresh), return_grad_map)
+            return loss, g
+        loss, g = K.EdgeLossKindFn.apply(output, gt_edge, gt_normals if is_grad else None, gt_mask, self.loss_kind, self.dice,
+                                         self.weight, self.depth_edges_loss_pos_to_neg_weight, from_inv_depth, is_grad, is_sigmoid,
+                                         float(sigmoid_thresh), return_grad_map)
         return loss, g
