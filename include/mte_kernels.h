@@ -318,6 +318,27 @@ int mte_edge_loss_kind_bwd(const float* pred, const float* edge, const float* no
                            float* dpred, int B, int H, int W, int kind, int dice, int from_inv, int is_grad, int is_sigmoid, float thresh,
                            mte_stream_t stream);                                          /* autograd of grad_loss.py:122-156 */
 
+/* ---- the supervised losses of SupervisedLoss (losses/supervised_loss.py:13-216) over up to four scales, all scales in one launch:
+ *      method 0 'l1', 1 'mse', 2 'berhu' (sparse only), 3 'silog', 4 'abs_rel' (get_loss_func's suffix order); sparse != 0 keeps the
+ *      pixels with a valid ground truth.  loss = sum_s f(pred_s + 1e-5, depth2inv(depth) at the nearest pixel of scale s) / nscales.
+ *   scales: nscales (1..4) mte_sup_scale, fp32 [B,H,W] maps; dpred is read by the backward only.  depth: metric depth [B,Hd,Wd], 0 = invalid.
+ *   work : mte_supervised_loss_work_elems(scales, nscales, B) doubles, 16-byte aligned (content on entry ignored: the forward clears its tickets)
+ *   fwd  : loss[1] <- the loss scalar; scale_loss [nscales] (nullable) <- the per-scale values; coef [16] <- backward coefficients
+ *          (computed on the device by the last workgroup; no host sync).  BerHu runs two launches.
+ *   bwd  : every pixel of every dpred_s <- gout * d loss / d pred_s, exact zeros where the mask drops a pixel (gout: device scalar, nullable = 1) */
+typedef struct { const float* pred; float* dpred; int H; int W; } mte_sup_scale;
+long mte_supervised_loss_work_elems(const void* scales, int nscales, int B);   /* two tickets, the BerHu hand-over, one record per 4096 pixels */
+int mte_supervised_loss_fwd(const void* scales, int nscales, int B, const float* depth, int Hd, int Wd, int method, int sparse,
+                            double* work, float* loss, float* scale_loss, float* coef, mte_stream_t stream);   /* supervised_loss.py:155-216 */
+int mte_supervised_loss_bwd(const void* scales, int nscales, int B, const float* depth, int Hd, int Wd, int method, int sparse,
+                            const float* coef, const float* gout, mte_stream_t stream);                       /* autograd of the same */
+/* F.interpolate(x, size = (H, W), mode = 'nearest') of upsample_output (model_utils.py:154-176) for up to four maps in one launch, integer
+ * ratios only (H % h == 0, W % w == 0; anything else is MTE_ERR_ARG).  fwd: dst [B,H,W] <- src [B,h,w], bit-equal to torch;
+ * bwd: dst [B,h,w] <- adjoint applied to src [B,H,W], each block summed row-major, no atomics */
+typedef struct { const float* src; float* dst; int h; int w; } mte_upsample_map;
+int mte_upsample_nearest_fwd(const void* maps, int nmaps, int B, int H, int W, mte_stream_t stream);
+int mte_upsample_nearest_bwd(const void* maps, int nmaps, int B, int H, int W, mte_stream_t stream);
+
 /* F.interpolate(pred, size = label size, mode = 'bilinear') of GradLoss.forward (grad_loss.py:127; identity on the multi-scale
  * training path, where every scale is compared at its own resolution) and its adjoint; fp32 [B,h,w] -> [B,H,W] */
 int mte_resize_bilinear_fwd(const float* x, float* y, int B, int h, int w, int H, int W, mte_stream_t stream);

@@ -192,6 +192,98 @@ class SilogFn(torch.autograd.Function):
         return dinv, None
 
 
+class _SupScale(ctypes.Structure):        # mte_sup_scale of include/mte_kernels.h
+    _fields_ = [("pred", ctypes.c_void_p), ("dpred", ctypes.c_void_p), ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+class _UpsampleMap(ctypes.Structure):     # mte_upsample_map of include/mte_kernels.h
+    _fields_ = [("src", ctypes.c_void_p), ("dst", ctypes.c_void_p), ("h", ctypes.c_int), ("w", ctypes.c_int)]
+
+
+# supervised methods in the order get_loss_func tests the suffixes (supervised_loss.py:73-87): the id the kernels take
+SUPERVISED_METHODS = ('l1', 'mse', 'berhu', 'silog', 'abs_rel')
+
+
+class SupervisedLossFn(torch.autograd.Function):
+    """sum_s f(inv_s + 1e-5, depth2inv(depth) nearest-resized to scale s) / n over the n = len(inv_depths) <= 4 scales
+    (SupervisedLoss.calculate_loss / forward, supervised_loss.py:155-216).  method: index into SUPERVISED_METHODS; sparse keeps the
+    pixels with depth > 0.  depth: metric depth [B,1,Hd,Wd] of any size.  One forward launch (two for BerHu) and one backward launch."""
+
+    @staticmethod
+    def forward(ctx, method, sparse, depth, *inv_depths):
+        preds = [p.contiguous().float() for p in inv_depths]
+        depth = depth.contiguous().float()
+        _K._require_gpu(preds[0])
+        B = preds[0].shape[0]
+        if not 1 <= len(preds) <= 4:
+            raise MteError("1 to 4 scales, got %d" % len(preds))
+        for p in preds + [depth]:
+            if p.dim() != 4 or p.shape[0] != B or p.shape[1] != 1:
+                raise MteError("maps must be [B,1,H,W] with one B, got %s" % (tuple(p.shape),))
+        arr = SupervisedLossFn._scales(preds, None)
+        dev = preds[0].device
+        work = torch.empty((_K.lib.mte_supervised_loss_work_elems(ctypes.addressof(arr), len(preds), B),), dtype=torch.float64, device=dev)
+        coef = torch.empty((16,), dtype=torch.float32, device=dev)
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        _K.lib.mte_supervised_loss_fwd(ctypes.addressof(arr), len(preds), B, depth.data_ptr(), depth.shape[2], depth.shape[3], int(method),
+                                       int(sparse), work.data_ptr(), loss.data_ptr(), None, coef.data_ptr(), _K._stream())
+        ctx.save_for_backward(depth, coef, *preds)
+        ctx.cfg = (int(method), int(sparse))
+        return loss
+
+    @staticmethod
+    def _scales(preds, dpreds):
+        arr = (_SupScale * len(preds))()
+        for i, (o, p) in enumerate(zip(arr, preds)):
+            o.pred, o.dpred, o.H, o.W = p.data_ptr(), (None if dpreds is None else dpreds[i].data_ptr()), p.shape[2], p.shape[3]
+        return arr
+
+    @staticmethod
+    def backward(ctx, gloss):
+        depth, coef, *preds = ctx.saved_tensors
+        dpreds = [torch.empty_like(p) for p in preds]
+        arr = SupervisedLossFn._scales(preds, dpreds)
+        gl = gloss.contiguous().float()
+        _K.lib.mte_supervised_loss_bwd(ctypes.addressof(arr), len(preds), preds[0].shape[0], depth.data_ptr(), depth.shape[2], depth.shape[3],
+                                       *ctx.cfg, coef.data_ptr(), gl.data_ptr(), _K._stream())
+        return (None, None, None) + tuple(dpreds)
+
+
+class NearestUpsampleFn(torch.autograd.Function):
+    """[F.interpolate(x, size=(H, W), mode='nearest') for x in maps] for fp32 [B,1,h,w] maps with H % h == 0 and W % w == 0 -- the
+    upsample_depth_maps step of SfmModel (model_utils.py:154-176).  One forward and one backward launch for all maps."""
+
+    @staticmethod
+    def forward(ctx, H, W, *maps):
+        xs = [m.contiguous().float() for m in maps]
+        _K._require_gpu(xs[0])
+        B = xs[0].shape[0]
+        if not 1 <= len(xs) <= 4:
+            raise MteError("1 to 4 maps, got %d" % len(xs))
+        for x in xs:
+            if x.dim() != 4 or x.shape[0] != B or x.shape[1] != 1:
+                raise MteError("maps must be [B,1,h,w] with one B, got %s" % (tuple(x.shape),))
+        ys = [torch.empty((B, 1, H, W), dtype=torch.float32, device=x.device) for x in xs]
+        arr = (_UpsampleMap * len(xs))()
+        for o, x, y in zip(arr, xs, ys):
+            o.src, o.dst, o.h, o.w = x.data_ptr(), y.data_ptr(), x.shape[2], x.shape[3]
+        _K.lib.mte_upsample_nearest_fwd(ctypes.addressof(arr), len(xs), B, int(H), int(W), _K._stream())
+        ctx.sizes = [(x.shape[2], x.shape[3]) for x in xs]
+        ctx.HW = (B, int(H), int(W))
+        return tuple(ys)
+
+    @staticmethod
+    def backward(ctx, *gys):
+        B, H, W = ctx.HW
+        gs = [g.contiguous().float() for g in gys]
+        dxs = [torch.empty((B, 1, h, w), dtype=torch.float32, device=gs[0].device) for h, w in ctx.sizes]
+        arr = (_UpsampleMap * len(gs))()
+        for o, g, d, (h, w) in zip(arr, gs, dxs, ctx.sizes):
+            o.src, o.dst, o.h, o.w = g.data_ptr(), d.data_ptr(), h, w
+        _K.lib.mte_upsample_nearest_bwd(ctypes.addressof(arr), len(gs), B, H, W, _K._stream())
+        return (None, None) + tuple(dxs)
+
+
 def adam_step_flat(p, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, gscale=1.0):
     """In-place fused Adam over flat fp32 device buffers."""
     _K._require_gpu(p)

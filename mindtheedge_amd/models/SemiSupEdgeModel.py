@@ -2,6 +2,8 @@
 for packnet_sfm/models/SemiSupEdgeModel.py (forward :98-162, compute_edge_loss_with_all_scales :164-198).
 
 loss = supervised_loss_weight * silog(inv_0, depth) + depth_edges_loss_weight * mean_s GradLoss(inv2depth(inv_s), edge_s, normal_s)
+in the shipped configuration; every other supervised method / scale count of SupervisedLoss and upsample_depth_maps (SfmModel) take the
+per-scale path, where GradLoss resizes each full-resolution map down to its label.
 
 Differences from the reference, all behaviour-preserving for the shipped configuration:
   * 'input_depth' is not forwarded to the depth network: the RGB+LiDAR pass it triggers upstream never reaches

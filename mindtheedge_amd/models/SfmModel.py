@@ -3,7 +3,7 @@
 import random
 
 from .base_model import BaseModel
-from .model_utils import flip_batch_input, flip_output
+from .model_utils import flip_batch_input, flip_output, upsample_output
 
 
 class SfmModel(BaseModel):
@@ -14,9 +14,7 @@ class SfmModel(BaseModel):
         self.pose_net = pose_net
         self.rotation_mode = rotation_mode
         self.flip_lr_prob = flip_lr_prob
-        self.upsample_depth_maps = upsample_depth_maps
-        if upsample_depth_maps:
-            raise NotImplementedError("upsample_depth_maps=True is not used by the shipped edge-loss configs")
+        self.upsample_depth_maps = upsample_depth_maps      # training only: every inverse-depth map at the size of scale 0
         self._network_requirements = ['depth_net', 'pose_net']
 
     def add_depth_net(self, depth_net):
@@ -55,7 +53,10 @@ class SfmModel(BaseModel):
             flag_flip_lr = self.draw_flip() if self._pinned_flip is None else self._pinned_flip
         else:
             flag_flip_lr = force_flip
-        return self.depth_net_flipping(batch, flag_flip_lr, output_features)
+        output = self.depth_net_flipping(batch, flag_flip_lr, output_features)
+        if self.training and self.upsample_depth_maps:        # reference SfmModel.py:92-94, after the flip
+            output = upsample_output(output)
+        return output
 
     def forward(self, batch, return_logs=False, force_flip=False, output_features=False):
         depth_output = self.compute_depth_net(batch, force_flip=force_flip, output_features=output_features)

@@ -32,6 +32,25 @@ def flip_output(output):
     return out
 
 
+def upsample_output(output):
+    """upsample_output(output, mode='nearest') (reference model_utils.py:154-176): every 'inv_depths' map nearest-upsampled to the size
+    of scale 0, scales 1.. in one launch (kernels.NearestUpsampleFn).  Scale 0 is passed through: the reference's same-size interpolate
+    is a copy.  PackNetSAN01 returns neither 'uncertainty' nor 'inv_depths_context'; they are not built."""
+    from .. import kernels as K
+    if 'uncertainty' in output or 'inv_depths_context' in output:
+        raise NotImplementedError("upsampling 'uncertainty' / 'inv_depths_context' is not built (PackNetSAN01 returns neither)")
+    if 'inv_depths' not in output:
+        return output
+    inv = list(output['inv_depths'])
+    H, W = inv[0].shape[-2:]
+    rest = [i for i, t in enumerate(inv[1:], 1) if tuple(t.shape[-2:]) != (H, W)]
+    if rest:
+        ups = K.NearestUpsampleFn.apply(H, W, *[inv[i] for i in rest])
+        for i, u in zip(rest, ups):
+            inv[i] = u
+    return {**output, 'inv_depths': inv}
+
+
 def merge_outputs(*outputs):
     merged = {'metrics': {}}
     for output in outputs:
