@@ -80,6 +80,7 @@ int mte_set_option(int option, int value);
  * (No reference counterpart: the reference's GroupNorm is one cuDNN call, layers01.py:32.) */
 #define MTE_DEVERR_GN_CLUSTER_FWD 1
 #define MTE_DEVERR_GN_CLUSTER_BWD 2
+#define MTE_DEVERR_IMAGE_RESAMPLE 4 /* mte_image_resample_u8 was handed tables whose tap span exceeds that of the LANCZOS tables of (in, out) */
 int mte_device_error_init(void);
 int mte_device_error_poll(void);
 /* weight gradient of the same conv into dw_stage = `stage_parts` x [N][KH*KW][Cin_p] fp32 (overwritten).  The reduction over
@@ -472,6 +473,32 @@ int mte_feat_l2(const void* a, long lda, const void* b, long ldb, double* sum, v
 int mte_edge_target_from_u8(const unsigned char* src, float* dst, long n, mte_stream_t stream);
 int mte_normal_target_from_u8(const unsigned char* src, float* dst, long n, mte_stream_t stream);
 int mte_resize_depth_preserve(const float* src, int B, int h, int w, float* dst, int H, int W, int* winner_ws, mte_stream_t stream);
+
+/* ---- training-image preparation (the 8-bit image half of datasets/transforms.py:17-50), bit for bit as PIL computes it
+ * mte_image_resample_u8: Image.crop + Image.resize((out_w, out_h), LANCZOS) of an 8-bit RGB frame (HWC): PIL's ImagingResample, horizontal
+ *   pass then vertical pass, each clipped to uint8.  src / src_stride (bytes) describe the whole frame, (crop_x, crop_y, in_w, in_h) the
+ *   window the filter reads; it never reads outside of it.  kk_* are the 22-bit fixed-point coefficients int32 [out][ksize_*] and
+ *   bounds_* the int32 [out][2] (first tap, tap count) of PIL's precompute_coeffs + normalize_coeffs_8bpc, on the device
+ *   (datasets/image_prep.py::lanczos_coeffs builds them on the host in double precision); the identity table (ksize 1, 1 << 22) skips a pass.
+ *   One launch with the intermediate rows in LDS when a tile's tap span fits, otherwise (or with two_pass != 0) two launches with a uint8
+ *   [in_h][out_w][3] intermediate in `workspace`: mte_image_resample_work_bytes gives its size, 0 = none needed.  Same bytes either way.
+ *   The tables MUST be the LANCZOS tables of exactly (in_w, out_w) / (in_h, out_h): the library sizes its LDS tiles from a bound of their tap
+ *   span and cannot read them on the host.  With tables of a wider filter the one-launch form leaves tiles unwritten and sets
+ *   MTE_DEVERR_IMAGE_RESAMPLE in the device error word (mte_device_error_poll) while the call itself returns MTE_OK.
+ * mte_color_jitter_u8_to_f32: torchvision-on-PIL adjust_brightness / adjust_contrast / adjust_saturation / adjust_hue in a per-sample order
+ *   on uint8 [B,H,W,3], each rounding to uint8 like PIL, then ToTensor: out = float32(u8) / 255 as [B,3,H,W]; out_original (may be null)
+ *   receives the un-jittered frame.  factors: float [B][4] = brightness, contrast, saturation factor and the uint8 added to the H channel
+ *   (trunc(hue_factor * 255) mod 256); order: int32 [B][4] operation ids (0 brightness, 1 contrast, 2 saturation, 3 hue) in the order they
+ *   are applied, -1 = none; order == null: plain ToTensor.  any_contrast != 0 when some sample applies contrast: luma_sums (B 64-bit
+ *   words, zero on entry) then receives the per-sample sum of the L channel in a first launch (integer atomics: exact, deterministic).
+ *   Contract: any_contrast MUST be non-zero if any row of `order` holds 1 -- the table lives on the device, the entry point cannot check it;
+ *   with any_contrast == 0 such a sample is blended towards a mean of 0. */
+long mte_image_resample_work_bytes(int in_h, int in_w, int out_h, int out_w, int two_pass);
+int mte_image_resample_u8(const unsigned char* src, long src_stride, int crop_x, int crop_y, int in_h, int in_w, unsigned char* dst,
+                          int out_h, int out_w, const int* kk_h, const int* bounds_h, int ksize_h, const int* kk_v, const int* bounds_v,
+                          int ksize_v, unsigned char* workspace, int two_pass, mte_stream_t stream);
+int mte_color_jitter_u8_to_f32(const unsigned char* in, int B, int H, int W, const float* factors, const int* order, int any_contrast,
+                               unsigned long long* luma_sums, float* out, float* out_original, mte_stream_t stream);
 
 #ifdef MTE_DEV
 /* Development knobs for same-box A/B measurements (tools/sweep.sh) and kernel-variant cross-checks (tests/).  NOT part of the

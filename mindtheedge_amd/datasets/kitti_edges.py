@@ -114,9 +114,10 @@ def prepare_edge_sample(edge_maps_u8, normal_maps_u8, shape):
 
 
 # ---- a reader on top of the formats above -------------------------------------------------------------------------------
-# File decoding is host I/O (PIL / numpy, the reference uses PIL and cv2.imread); everything after it -- sparse resizes,
-# target scaling, de-quantisation -- runs on the device through the functions above.  Not rebuilt: colour jitter, random
-# crops, context frames, the .bin velodyne projection (pass depth / lidar maps as 16-bit PNG or .npy).
+# File decoding is host I/O (PIL / numpy, the reference uses PIL and cv2.imread); everything after it -- the crop, the LANCZOS
+# resize of the frame, colour jitter and ToTensor (image_prep.py), sparse resizes, target scaling, de-quantisation -- runs on the
+# device.  Not rebuilt: the colour matrix, LiDAR value perturbation (augment_depth_values), context frames, the .bin velodyne
+# projection (pass depth / lidar maps as 16-bit PNG or .npy).
 
 def _read_gray_u8(path):
     """cv2.imread(path)[:, :, 0] of the reference for the 8-bit single-channel annotation PNGs."""
@@ -142,15 +143,22 @@ def read_png_depth(path):
 
 
 class KittiEdgeSplitDataset:
-    """One sample per split-file line: rgb (PIL-resized to ``image_shape`` like the reference's resize_image, /255),
-    depth (resize_depth_preserve), edge / edge_1..3 and normal / normal_1..3 targets.  ``__getitem__`` returns device
-    tensors shaped like the reference's collated sample with batch size 1 removed: rgb [3,H,W], depth [1,H,W], ..."""
+    """One sample per split-file line: rgb (cropped, LANCZOS-resized to ``image_shape`` like the reference's resize_image, colour
+    jittered, /255 -- on the device, image_prep.py), depth (resize_depth_preserve), edge / edge_1..3 and normal / normal_1..3 targets.
+    ``__getitem__`` returns device tensors shaped like the reference's collated sample with batch size 1 removed: rgb [3,H,W],
+    depth [1,H,W], ...
 
-    def __init__(self, split_file, image_shape, device='cuda', root=''):
+    jittering = (brightness, contrast, saturation, hue) draws the reference's colour jitter per sample from Python's ``random``
+    (the sample then also carries the un-jittered ``rgb_original``); crop_train_borders crops rgb, depth, edge and normal
+    before the resize like crop_sample.  Both default to () = off."""
+
+    def __init__(self, split_file, image_shape, device='cuda', root='', jittering=(), crop_train_borders=()):
         self.records = read_split(split_file)
         self.shape = (int(image_shape[0]), int(image_shape[1]))
         self.device = torch.device(device)
         self.root = root
+        self.jittering = tuple(jittering or ())
+        self.crop_train_borders = tuple(crop_train_borders or ())
 
     def __len__(self):
         return len(self.records)
@@ -158,26 +166,42 @@ class KittiEdgeSplitDataset:
     def _p(self, path):
         return path if os.path.isabs(path) or not self.root else os.path.join(self.root, path)
 
+    def _u8_map(self, path, borders):
+        import numpy as np
+        a = _read_gray_u8(path)
+        if borders is not None:
+            a = a[borders[1]:borders[3], borders[0]:borders[2]]               # crop_depth, augmentations.py:425-444
+        return torch.from_numpy(np.ascontiguousarray(a).astype(np.uint8)).to(self.device)
+
     def __getitem__(self, idx):
         import numpy as np
         from PIL import Image
+        from . import image_prep as ip
         rec = self.records[idx]
         H, W = self.shape
         img = Image.open(self._p(rec['rgb'])).convert('RGB')
-        if img.size != (W, H):
-            img = img.resize((W, H), Image.LANCZOS)                       # transforms.Resize(shape, ANTIALIAS), augmentations.py:16-35
-        rgb = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(self.device).permute(2, 0, 1).float() / 255.0
-        sample = {'idx': idx, 'rgb': rgb}
+        borders = ip.parse_crop_borders(self.crop_train_borders, img.size[::-1]) if self.crop_train_borders else None
+        frame = torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(self.device)
+        if borders is not None or img.size != (W, H):
+            frame = ip.resize_image_u8(frame, (H, W), crop=borders)          # crop_image + transforms.Resize(shape, ANTIALIAS), augmentations.py:16-35
+        params = ip.draw_color_jitter(self.jittering)
+        sample = {'idx': idx}
+        if self.jittering:
+            rgb, original = ip.color_jitter_to_tensor(frame.unsqueeze(0), [params], want_original=True)
+            sample['rgb'], sample['rgb_original'] = rgb[0], original[0]
+        else:
+            sample['rgb'] = ip.color_jitter_to_tensor(frame.unsqueeze(0))[0]
         if rec.get('depth'):
-            d = torch.from_numpy(read_png_depth(self._p(rec['depth']))).to(self.device)
-            sample['depth'] = resize_depth_preserve(d, self.shape).unsqueeze(0)
+            d = read_png_depth(self._p(rec['depth']))
+            if borders is not None:
+                d = np.ascontiguousarray(d[borders[1]:borders[3], borders[0]:borders[2]])
+            sample['depth'] = resize_depth_preserve(torch.from_numpy(d).to(self.device), self.shape).unsqueeze(0)
         edges, normals = [], []
+        # crop_sample crops 'edge' and 'normal' only: the coarser scales keep their frame (augmentations.py:512-518)
         if rec.get('edge'):
-            edges = [torch.from_numpy(np.ascontiguousarray(_read_gray_u8(p)).astype(np.uint8)).to(self.device)
-                     for p in multiscale_paths(self._p(rec['edge']))]
+            edges = [self._u8_map(p, borders if s == 0 else None) for s, p in enumerate(multiscale_paths(self._p(rec['edge'])))]
         if rec.get('normal'):
-            normals = [torch.from_numpy(np.ascontiguousarray(_read_gray_u8(p)).astype(np.uint8)).to(self.device)
-                       for p in multiscale_paths(self._p(rec['normal']))]
+            normals = [self._u8_map(p, borders if s == 0 else None) for s, p in enumerate(multiscale_paths(self._p(rec['normal'])))]
         sample.update(prepare_edge_sample(edges, normals, self.shape))
         return sample
 
@@ -211,13 +235,23 @@ class SplitLoader:
             yield collate([self.ds[j] for j in mine[i * self.bs:(i + 1) * self.bs]])
 
 
+def _as_tuple(v):
+    """a YAML list, a tuple or the reference's string form '(0.2, 0.2, 0.2, 0.05)' -> tuple; None / '' -> ()"""
+    if v is None or v == '':
+        return ()
+    return tuple(eval(v)) if isinstance(v, str) else tuple(v)
+
+
 def make_loader(config, rank, world):
     """``train_edges.py --data mindtheedge_amd.datasets.kitti_edges:make_loader``: config.datasets.train.split[0] is the
-    8-column split file, config.datasets.train.path[0] (optional) the root folder of its relative paths."""
+    8-column split file, config.datasets.train.path[0] (optional) the root folder of its relative paths;
+    config.datasets.augmentation.jittering / .crop_train_borders as in the reference (default (): off)."""
     tr = config.datasets.train
     shape = config.datasets.augmentation.image_shape
     shape = eval(shape) if isinstance(shape, str) else tuple(shape)
     root = (tr.get('path') or [''])[0] if isinstance(tr.get('path'), (list, tuple)) else (tr.get('path') or '')
     split = tr['split'][0] if isinstance(tr['split'], (list, tuple)) else tr['split']
-    ds = KittiEdgeSplitDataset(split, shape, device=torch.device('cuda', torch.cuda.current_device()), root=root)
+    aug = config.datasets.augmentation
+    ds = KittiEdgeSplitDataset(split, shape, device=torch.device('cuda', torch.cuda.current_device()), root=root,
+                               jittering=_as_tuple(aug.get('jittering')), crop_train_borders=_as_tuple(aug.get('crop_train_borders')))
     return SplitLoader(ds, int(tr.batch_size), rank, world)

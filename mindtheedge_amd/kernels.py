@@ -303,7 +303,8 @@ class _ZeroArena:
 
 _arena = _ZeroArena()
 _DEVERR_NAMES = {1: "GroupNorm cluster kernel (forward): a workgroup of a cluster never arrived",
-                 2: "GroupNorm cluster kernel (backward): a workgroup of a cluster never arrived"}
+                 2: "GroupNorm cluster kernel (backward): a workgroup of a cluster never arrived",
+                 4: "image resample: coefficient tables wider than the LANCZOS tables of the given sizes, output tiles left unwritten"}
 
 
 def _device_errors_init():

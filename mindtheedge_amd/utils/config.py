@@ -35,7 +35,9 @@ _DEFAULTS = {
     'edges': {'train_depth_edges': True, 'depth_edges_loss_weight': 10.0, 'use_external_edges_for_loss': True,
               'edge_loss_type': 'cross_entropy', 'edge_loss_class_list_to_mask_out': [],
               'depth_edge_loss_pos_to_neg_weight': 1.0},
-    'datasets': {'augmentation': {'image_shape': (384, 1280)}, 'train': {'batch_size': 8}},
+    # jittering / crop_train_borders: () = off.  The reference's default_config.py:166 jitters with (0.2, 0.2, 0.2, 0.05) and crops
+    # nothing; a run that wants the reference's recipe sets  datasets.augmentation.jittering: [0.2, 0.2, 0.2, 0.05]  in its YAML.
+    'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': ()}, 'train': {'batch_size': 8}},
     'checkpoint': {'filepath': '', 'save_top_k': -1},
 }
 
