@@ -109,7 +109,8 @@ int mte_pack_conv_weights_bwd(const void* wfwd, void* wbwd, int Cout, int KH, in
 /* sum of the `parts` partial stages -> OIHW fp32 gradient (drops channel padding).  The stage is scratch: with more than 32 parts
  * (LDS-patch weight gradient: one slab per workgroup) a parallel first level adds parts 1.. into part 0 before the transpose. */
 int mte_unpack_conv_wgrad(float* dw_stage, int parts, float* dw_oihw, int Cout, int Cin, int KH, int KW, int Cin_p, mte_stream_t stream);
-/* out[N] = column sums of y[M][N] (conv bias gradient) */
+/* out[N] (overwritten) = column sums of y[M][N] (conv bias gradient).  N % 8 == 0 and at most 256 16-byte chunks per row (2048 bf16 / 1024 fp32
+ * columns): more is MTE_ERR_UNSUPPORTED and leaves `out` as it was */
 int mte_colsum(const void* y, long ld, long M, int N, float* out, int dtype, mte_stream_t stream);
 
 /* ---- LDS-patch convolution for the high-resolution, few-channel layers (bf16, C_out <= 64, W % 32 == 0, k in {1,3,5,7}):
@@ -244,6 +245,8 @@ int mte_invdepth_bwd_weight(const void* x, long ldx, const float* dlogit, float*
 int mte_rank1_conv_fwd(const float* inv, const float* w, long w_stride, void* y, long ldy, int B, int h, int wl, int N, int dtype, mte_stream_t stream);
 int mte_rank1_conv_bwd_data(const void* dy, long lddy, const float* w, long w_stride, float* dinv, int B, int h, int wl, int N, int accumulate, int dtype,
                             mte_stream_t stream);
+/* out [B,2h,2w] = nearest_up2(inv), fp32.  No host caller since the rank-1 weight gradient up-samples the map on its way into LDS (tap_wgrad.hip);
+ * kept as part of the exported surface. */
 int mte_upsample2_f32(const float* inv, float* out, int B, int h, int wl, mte_stream_t stream);
 /* _fwd fused into the LDS-patch 3x3 forward (bf16, N <= 64): y = conv_3(x, wpatch) + bias + conv_1(nearest_up2(inv), w1) in ONE launch -- the store loop of a
  * tile adds the term from two small LDS tables (the map under the tile + halo, the 9 x N weights), so y is neither written first nor read back.  inv [B,H/2,W/2];
@@ -271,7 +274,7 @@ int mte_copy_channels(const void* src, long lds_, void* dst, long ldd, long npix
  * dst0[0..n0) = src[0..n0), dst1[0..n1) = src[n0..n0+n1) */
 int mte_split_record(const float* src, float* dst0, int n0, float* dst1, int n1, mte_stream_t stream);
 /* out = a + b over NHWC channel-slice views: the summed gradient of an activation with two consumers (what autograd's
- * implicit accumulation does in the reference), one 16-byte-vectorised pass whatever the strides */
+ * implicit accumulation does in the reference), one 16-byte-vectorised pass whatever the strides.  `out` may be `a` itself (same pointer and stride) */
 int mte_add_channels(const void* a, long lda, const void* b, long ldb, void* out, long ldo, long npix, int C, int dtype, mte_stream_t stream);
 
 /* ---- depth-edge loss: inv2depth + GradLayer + GradLoss('cross_entropy')
