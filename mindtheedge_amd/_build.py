@@ -49,18 +49,23 @@ def _stamp(target, digest):
 DEV_LIB = os.path.join(CSRC, "libmte_hip_dev.so")
 
 
+def headers(csrc=CSRC):
+    """Every header a source can include: all of csrc/*.hpp, in a fixed order.  Each object's digest covers them all, so that editing any
+    header recompiles (a few objects more than strictly needed, never one fewer)."""
+    return sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".hpp"))
+
+
 def build(force=False, verbose=False, dev=True):
     """Compile every .hip for gfx950 and link the C-ABI shared library next to the sources (and, dev=True, its -DMTE_DEV twin)."""
     hipcc = _hipcc()
-    hdr = os.path.join(CSRC, "common.hpp")
-    hdr2 = os.path.join(CSRC, "conv_args.hpp")
+    hdrs = headers()
     os.makedirs(os.path.join(CSRC, "dev"), exist_ok=True)
     variants = [("", [], LIB)] + ([("dev", ["-DMTE_DEV"], DEV_LIB)] if dev else [])
     jobs = []
     for sub, extra, _ in variants:
         for s in SOURCES:
             src, obj = os.path.join(CSRC, s), os.path.join(CSRC, sub, s.replace(".hip", ".o"))
-            dig = _digest([src, hdr, hdr2], " ".join(FLAGS + extra))
+            dig = _digest([src] + hdrs, " ".join(FLAGS + extra))
             if force or _stale(obj, dig):
                 jobs.append(([hipcc] + FLAGS + extra + ["-c", src, "-o", obj], obj, dig))
 

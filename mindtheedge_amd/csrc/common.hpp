@@ -79,6 +79,20 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
 }
+// wave-wide sum, every lane ends with the total: xor butterfly over quad_perm / row_half_mirror / row_mirror DPP operands (lanes 1, 2, 4, 8 apart)
+// and the two lane-swap instructions of gfx950 (rows, then halves) -- 6 adds + 2 swaps instead of 6 ds_bpermute round trips
+__device__ __forceinline__ float wave_sum_dpp(float v) {
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));    // row_half_mirror
+    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));    // row_mirror
+    const unsigned u = __builtin_bit_cast(unsigned, v);
+    auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);          // {rows 0 0 2 2, rows 1 1 3 3}
+    v = __builtin_bit_cast(float, (unsigned)r16[0]) + __builtin_bit_cast(float, (unsigned)r16[1]);
+    const unsigned w = __builtin_bit_cast(unsigned, v);
+    auto r32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);          // {lower half twice, upper half twice}
+    return __builtin_bit_cast(float, (unsigned)r32[0]) + __builtin_bit_cast(float, (unsigned)r32[1]);
+}
 
 __device__ __forceinline__ float elu1(float u) { return u > 0.f ? u : (__expf(u) - 1.f); }
 
@@ -143,10 +157,7 @@ __device__ __forceinline__ void mte_report_device_error(unsigned* err, unsigned 
     //  any non-zero value fails the step)
     if (err) __hip_atomic_store(err, __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) | code, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-// mte_set_option(MTE_OPT_HANDOFF_FENCES, v): the last-arriver hand-offs of the read-only kernels (GroupNorm statistics, loss sums) draw their
-// ticket with an agent-scope RELEASE and the last arriver issues an agent-scope ACQUIRE before it reads the records.  The records themselves
-// are returning atomic exchanges / agent-scope atomic loads (performed at the memory side, never served from a CU's L1), which is the form
-// MI355X_MICROARCH.md's visibility table lists as measured-valid; the fences make the protocol independent of that table.  Defined in norm_act.hip.
+// mte_set_option(MTE_OPT_HANDOFF_FENCES, v): see handoff.hpp.  Defined in norm_act.hip.
 extern int g_mte_handoff_fences;
 // mte_set_option(MTE_OPT_WGRAD_SHARES_CHIP, v): 1 = the caller queues the weight-gradient launches on a stream of their own beside the data-gradient chain (the
 // host side of this repository does): the MFMA weight-gradient kernels then aim for HALF a chip of workgroups (profiles/r05_side_queue_width.txt: same-box step

@@ -24,16 +24,15 @@
 // HBM-bound: 12 B/pixel forward (inv, edge, normal), 16 B/pixel backward (+4 B gradient write).
 #include "common.hpp"
 #include "edge_direction.hpp"
+#include "edge_tile.hpp"
+#include "handoff.hpp"
 
 int g_mte_loss_prezeroed = 0;
 
 namespace {
 
-constexpr int TW = 64, TH = 32;         // output tile (256 threads x 2 passes x 4 pixels)
-constexpr int LS = 72;                  // LDS row stride in floats: image column j of the tile sits at index 4 + j (16-byte aligned interior)
 constexpr int MAXS = 4;                 // scales per launch
 constexpr int NP = 13;                  // partial sums per workgroup: 6 edge sums, 4 mask statistics, 3 silog sums
-constexpr int REC = 16;                 // doubles per workgroup record (one 128-byte line)
 #ifndef MTE_EDGE_FWD_TILES
 #define MTE_EDGE_FWD_TILES 3
 #endif
@@ -62,128 +61,8 @@ struct EdgeMulti {
     const float* gt_depth;              // optional fused silog on scale 0: metric depth, 0 = invalid
     float* silog_loss; float* silog_aux;          // forward out: loss, (mean, 10/sqrt(S)/n)
     const float* silog_gout;            // backward: upstream gradient of the silog loss (device, nullable = 1)
-    int fences;                         // MTE_OPT_HANDOFF_FENCES (common.hpp): release before each ticket, acquire in the last arriver
+    int fences;                         // MTE_OPT_HANDOFF_FENCES (handoff.hpp)
 };
-
-// 1 / x as v_rcp_f32 (1 ulp) + one Newton step: r' = r + r (1 - x r), the two fmas of the IEEE division sequence without its scaling and
-// fix-up instructions (3 instructions instead of ~10).  x is in [1e-6, ~1e3] here -- no denormals, overflow or division by zero to fix up -- and
-// the result is within 1 ulp of the correctly rounded quotient (almost always equal to it).
-__device__ __forceinline__ float rcp_newton(float x) {
-    const float r = __builtin_amdgcn_rcpf(x);
-    return __builtin_fmaf(r, __builtin_fmaf(-x, r, 1.f), r);
-}
-#if defined(MTE_EDGE_ABLATE) && (MTE_EDGE_ABLATE & 4)
-__device__ __forceinline__ float to_depth(int from_inv, float v) { return from_inv ? 1.f / fmaxf(v, 1e-6f) : v; }   // diagnostic: the IEEE division of rounds 1-3
-#else
-__device__ __forceinline__ float to_depth(int from_inv, float v) { return from_inv ? rcp_newton(fmaxf(v, 1e-6f)) : v; }
-#endif
-
-// 4 consecutive floats of row `row` starting at column x (x % 4 == 0); zero beyond the image
-__device__ __forceinline__ f32x4_t load4(const float* base, long row, int x, int W, int vec) {
-    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) { if (x < W) v = *(const f32x4_t*)(base + row * W + x); }
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (x + k < W) v[k] = base[row * W + x + k];
-    }
-    return v;
-}
-__device__ __forceinline__ void store4(float* base, long row, int x, int W, int vec, const f32x4_t& v) {
-    if (vec) { if (x < W) *(f32x4_t*)(base + row * W + x) = v; }
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (x + k < W) base[row * W + x + k] = v[k];
-    }
-}
-
-// Depth tile: rows y0-R .. y0+TH+R-1, columns x0-R .. x0+TW+R-1 of sample b, staged as DEPTH into sd (row stride LS, column j
-// at 4 + j).  Two steps so that the loads are in flight together with the workgroup's other loads: issue -> registers, commit
-// -> reciprocal + LDS store.
-template <int R> struct DepthTile {
-    static constexpr int ROWS = TH + 2 * R;
-    static constexpr int NI = (ROWS * (TW / 4) + 255) / 256;      // interior float4 groups per thread
-    static_assert(ROWS * 2 * R <= 256, "one halo pixel per thread");
-    f32x4_t v[NI];
-    float hv;
-    __device__ __forceinline__ void issue(const EdgeScale& sc, int vec, int b, int x0, int y0) {
-        const float* img = sc.pred + (long)b * sc.H * sc.W;
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int i = threadIdx.x + k * 256;
-            const int ly = i >> 4, c4 = (i & 15) * 4;
-            const int gy = y0 + ly - R;
-            v[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (i < ROWS * (TW / 4) && (unsigned)gy < (unsigned)sc.H) v[k] = load4(img, gy, x0 + c4, sc.W, vec);
-        }
-        hv = 0.f;
-        const int i = threadIdx.x;
-        if (i < ROWS * 2 * R) {
-            const int ly = i / (2 * R), k = i % (2 * R);
-            const int j = k < R ? k - R : TW + (k - R);
-            const int gy = y0 + ly - R, gx = x0 + j;
-            if ((unsigned)gy < (unsigned)sc.H && (unsigned)gx < (unsigned)sc.W) hv = img[(long)gy * sc.W + gx];
-        }
-    }
-    __device__ __forceinline__ void commit(const EdgeScale& sc, int from_inv, int x0, int y0, float* sd) const {
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int i = threadIdx.x + k * 256;
-            if (i >= ROWS * (TW / 4)) break;
-            const int ly = i >> 4, c4 = (i & 15) * 4;
-            const bool rowok = (unsigned)(y0 + ly - R) < (unsigned)sc.H;
-            f32x4_t d;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = (rowok && x0 + c4 + e < sc.W) ? to_depth(from_inv, v[k][e]) : 0.f;
-            *(f32x4_t*)(sd + ly * LS + 4 + c4) = d;
-        }
-        const int i = threadIdx.x;
-        if (i < ROWS * 2 * R) {
-            const int ly = i / (2 * R), k = i % (2 * R);
-            const int j = k < R ? k - R : TW + (k - R);
-            const int gy = y0 + ly - R, gx = x0 + j;
-            sd[ly * LS + 4 + j] = ((unsigned)gy < (unsigned)sc.H && (unsigned)gx < (unsigned)sc.W) ? to_depth(from_inv, hv) : 0.f;
-        }
-    }
-};
-
-// the 3 x 6 window around 4 consecutive pixels: w[r][0..5] = columns c-1 .. c+4 of LDS rows (ly-1, ly, ly+1); c % 4 == 0
-__device__ __forceinline__ void window(const float* sd, int ly, int c, float w[3][6]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float* row = sd + (ly - 1 + r) * LS + 4 + c;
-        const f32x4_t m = *(const f32x4_t*)row;
-        w[r][0] = row[-1]; w[r][1] = m[0]; w[r][2] = m[1]; w[r][3] = m[2]; w[r][4] = m[3]; w[r][5] = row[4];
-    }
-}
-// Sobel responses of pixel k (0..3) of the window -- kernels of grad_loss.py:20-31
-__device__ __forceinline__ void sobel4(const float w[3][6], int k, float& sh, float& sv, float& srl, float& slr) {
-    const float n0 = w[0][k], n1 = w[0][k + 1], n2 = w[0][k + 2], n3 = w[1][k], n5 = w[1][k + 2], n6 = w[2][k], n7 = w[2][k + 1], n8 = w[2][k + 2];
-    sh = (n2 - n0) + 2.f * (n5 - n3) + (n8 - n6);
-    sv = (n6 - n0) + 2.f * (n7 - n1) + (n8 - n2);
-    srl = (n1 - n3) + 2.f * (n2 - n6) + (n5 - n7);
-    slr = (n5 - n1) + 2.f * (n8 - n0) + (n7 - n3);
-}
-// 1-ulp reciprocal (v_rcp_f32): enough wherever the result is not differenced against a neighbour (the depth tile keeps IEEE division)
-__device__ __forceinline__ float rcpf(float x) { return __builtin_amdgcn_rcpf(x); }
-// natural log / exp on the transcendental unit without the denormal-range scaling of __logf / __expf (5 extra instructions each): every
-// argument here is >= 1e-4 (p + 0.001, 10 (inv + 1e-5), 10 / depth), and an exp that underflows may flush to zero (1 + t follows)
-__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309f; }
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-
-// wave-wide sum, every lane ends with the total: xor butterfly over quad_perm / row_half_mirror / row_mirror DPP operands (lanes 1, 2, 4, 8 apart)
-// and the two lane-swap instructions of gfx950 (rows, then halves) -- 6 adds + 2 swaps instead of 6 ds_bpermute round trips
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));    // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));    // row_mirror
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);          // {rows 0 0 2 2, rows 1 1 3 3}
-    v = __builtin_bit_cast(float, (unsigned)r16[0]) + __builtin_bit_cast(float, (unsigned)r16[1]);
-    const unsigned w = __builtin_bit_cast(unsigned, v);
-    auto r32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);          // {lower half twice, upper half twice}
-    return __builtin_bit_cast(float, (unsigned)r32[0]) + __builtin_bit_cast(float, (unsigned)r32[1]);
-}
 
 struct BlockId { int s, b, t0, t1; };                            // tiles t0 .. t1 - 1 of sample b of scale s
 __device__ __forceinline__ BlockId decode_block(const EdgeMulti& a) {
@@ -207,7 +86,7 @@ __device__ __forceinline__ void forward_tail(const EdgeMulti& a, const BlockId& 
                                              float* sd, float (*sred)[NP], int* s_last_p) {
     const EdgeScale& sc = a.s[id.s];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    volatile int& s_last = *s_last_p;
+    volatile int* s_last = s_last_p;                               // handoff::arrive broadcasts through it
     // ---- sums.  fp32 per thread and per wave (xor butterfly in DPP / lane-swap instructions), fp64 from there on.  Round 4: NO atomic
     //      adds.  The workgroup leaves ONE record (its own 128-byte line); the last workgroup of a (scale, sample) to arrive adds that
     //      image's <= 240 records in a FIXED order and writes the image's sums; the last of those finishes the losses.  Every sum of the
@@ -224,23 +103,12 @@ __device__ __forceinline__ void forward_tail(const EdgeMulti& a, const BlockId& 
     __syncthreads();
     const bool live = tid < NP && !((tid >= 4 && tid < 10 && !has_mask) || (tid >= 10 && !silog));
     if (live) {
-        // RETURNING exchange: the value comes back only after the store has been performed at the memory side (a plain store, or a
-        // no-return atomic, is acknowledged earlier: the ticket below was seen to overtake it about once per few thousand workgroups)
         const double v = (double)sred[0][tid] + (double)sred[1][tid] + (double)sred[2][tid] + (double)sred[3][tid];
-        const unsigned long long before = atomicExch((unsigned long long*)(a.records + (long)blockIdx.x * REC) + tid, (unsigned long long)__double_as_longlong(v));
-        asm volatile("" ::"v"(before));
+        handoff::publish(a.records + (long)blockIdx.x * REC + tid, v);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
+    handoff::drain();
     const int per_image = sc.groups;                               // records (= workgroups) of this image
-    if (tid == 0) {
-        // (the kernel stores nothing but its records: a release fence here writes back no output lines of its own)
-        if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        s_last = __hip_atomic_fetch_add(a.counter + 1 + id.s * a.B + id.b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(per_image - 1);
-        if (s_last && a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!handoff::draw([&] { return a.counter + 1 + id.s * a.B + id.b; }, [&] { return per_image; }, a.fences, a.fences, s_last)) return;
     // ---- last workgroup of this (scale, sample): value v = tid % 16 of records k, k + 16, ... (k = tid / 16), then the 16 part sums in order
     {
         double* s_fin = (double*)sd;                               // the tile is dead (barriers above)
@@ -249,7 +117,7 @@ __device__ __forceinline__ void forward_tail(const EdgeMulti& a, const BlockId& 
         double part = 0.0;
         if (v < NP && !((v >= 4 && v < 10 && !has_mask) || (v >= 10 && !silog))) {
 #pragma unroll 4
-            for (int j = k; j < per_image; j += 16) part += __hip_atomic_load(rec + (long)j * REC, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int j = k; j < per_image; j += 16) part += handoff::read(rec + (long)j * REC);
         }
         s_fin[k * 16 + v] = part;
         __syncthreads();
@@ -257,18 +125,9 @@ __device__ __forceinline__ void forward_tail(const EdgeMulti& a, const BlockId& 
             double tot = 0.0;
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) tot += s_fin[kk * 16 + tid];
-            const unsigned long long before = atomicExch((unsigned long long*)(a.results + ((long)id.s * a.B + id.b) * NP) + tid, (unsigned long long)__double_as_longlong(tot));
-            asm volatile("" ::"v"(before));
+            handoff::publish(a.results + ((long)id.s * a.B + id.b) * NP + tid, tot);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-            s_last = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(a.nscales * a.B - 1);
-            if (s_last && a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        }
-        __syncthreads();
-        if (!s_last) return;
+        if (!handoff::arrive([&] { return a.counter; }, [&] { return a.nscales * a.B; }, a.fences, a.fences, s_last)) return;
     }
     finalize_losses(a, (double*)sd, (TH + 2) * LS / 2);
 }
@@ -389,7 +248,6 @@ __global__ __launch_bounds__(256, FAST ? 4 : 2) void edge_loss_fwd_kernel(EdgeMu
 // one L2 round trip each, one thread) that serial tail was ~45 us of a 73 us launch (round 4: forward 73 -> see profiles/README.md).  So the
 // whole workgroup first copies the sums into LDS (`stage`: the depth tile's storage, free by now; one round trip); one thread per
 // (scale, sample) does the divisions, one per scale the ordered sum (+ one for the silog loss, in another wave).
-__device__ __forceinline__ double acc_load(const double* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 // class-balance arithmetic of one scale from its image sums R[b * NP + i] (comp_cross_entropy, grad_loss.py:161-219)
 struct ScaleStats { bool binary; double nvalid, wneg_total; };
 template <typename V> __device__ __forceinline__ ScaleStats scale_stats(const V& R0, long R, int B, bool has_mask, double numel) {
@@ -424,7 +282,7 @@ template <typename V> __device__ __forceinline__ void silog_finish(const EdgeMul
     if (a.silog_aux) { a.silog_aux[0] = (float)m1; a.silog_aux[1] = (float)(10.0 / sqrt(S) / n1); }
 }
 struct LdsView { const double* l; __device__ __forceinline__ double operator()(long i) const { return l[i]; } };
-struct MemView { const double* g; __device__ __forceinline__ double operator()(long i) const { return acc_load(g + i); } };
+struct MemView { const double* g; __device__ __forceinline__ double operator()(long i) const { return handoff::read(g + i); } };
 
 __device__ void finalize_losses(const EdgeMulti& a, double* stage, int stage_elems) {
     const int tid = threadIdx.x;
@@ -434,7 +292,7 @@ __device__ void finalize_losses(const EdgeMulti& a, double* stage, int stage_ele
         // the usual case.  (1) sums -> LDS; (2) one thread per (scale, sample): alpha, the two coefficients (fp64 divisions -- done by one
         // thread per SCALE these were ~3 us of serial tail) and the sample's term of the loss; (3) one thread per scale adds the terms in order
         __syncthreads();                                          // every wave is done with the tile
-        for (int i = tid; i < n; i += 256) stage[i] = acc_load(a.results + i);
+        for (int i = tid; i < n; i += 256) stage[i] = handoff::read(a.results + i);
         __syncthreads();
         const LdsView R0{stage};
         double* term = stage + n;

@@ -20,17 +20,14 @@
 // alpha is known.  The backward recomputes p (and the box alpha) on the tile + halo, applies torch's BCE backward
 // w (p - t) / max(p (1 - p), 1e-12) / N (+ the dice derivative), the sigmoid derivative p (1 - p), the transposed direction-selected Sobel
 // stencil and the derivative of inv2depth.
-//
-// edge_loss.hip (the four-scale training launch) is left as it is; the small tile helpers below are restated from it.
 #include "common.hpp"
 #include "edge_direction.hpp"
+#include "edge_tile.hpp"
+#include "handoff.hpp"
 
 namespace {
 
-constexpr int TW = 64, TH = 32;         // output tile (256 threads x 2 passes x 4 pixels)
-constexpr int LS = 72;                  // LDS row stride in floats: image column j of the tile sits at index 4 + j
 constexpr int NP = 13;                  // partial sums per workgroup (see the forward kernel)
-constexpr int REC = 16;                 // doubles per workgroup record (one 128-byte line)
 constexpr int BR = 7;                   // box radius: 15 x 15 window
 constexpr int NC = 4;                   // leading backward coefficients: alpha, weight / N, dice c1, dice c2
 
@@ -48,110 +45,6 @@ struct KindArgs {
     float* coef;                        // forward out / backward in: [NC + 2B + 1]
     const float* gout;                  // backward: upstream gradient of the loss (device, nullable = 1)
 };
-
-// ---- tile helpers (as in edge_loss.hip) -----------------------------------------------------------------------------------------
-__device__ __forceinline__ float rcp_newton(float x) {
-    const float r = __builtin_amdgcn_rcpf(x);
-    return __builtin_fmaf(r, __builtin_fmaf(-x, r, 1.f), r);
-}
-__device__ __forceinline__ float to_depth(int from_inv, float v) { return from_inv ? rcp_newton(fmaxf(v, 1e-6f)) : v; }
-__device__ __forceinline__ float rcpf(float x) { return __builtin_amdgcn_rcpf(x); }
-__device__ __forceinline__ float fast_log(float x) { return __builtin_amdgcn_logf(x) * 0.693147180559945309f; }
-__device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }
-
-__device__ __forceinline__ f32x4_t load4(const float* base, long row, int x, int W, int vec) {
-    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
-    if (vec) { if (x < W) v = *(const f32x4_t*)(base + row * W + x); }
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (x + k < W) v[k] = base[row * W + x + k];
-    }
-    return v;
-}
-__device__ __forceinline__ void store4(float* base, long row, int x, int W, int vec, const f32x4_t& v) {
-    if (vec) { if (x < W) *(f32x4_t*)(base + row * W + x) = v; }
-    else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) if (x + k < W) base[row * W + x + k] = v[k];
-    }
-}
-
-// depth on rows y0-R .. y0+TH+R-1, columns x0-R .. x0+TW+R-1 of sample b -> sd (row stride LS, column j at 4 + j); issue -> registers, commit -> LDS
-template <int R> struct DepthTile {
-    static constexpr int ROWS = TH + 2 * R;
-    static constexpr int NI = (ROWS * (TW / 4) + 255) / 256;
-    static_assert(ROWS * 2 * R <= 256, "one halo pixel per thread");
-    f32x4_t v[NI];
-    float hv;
-    __device__ __forceinline__ void issue(const KindArgs& a, int b, int x0, int y0) {
-        const float* img = a.pred + (long)b * a.H * a.W;
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int i = threadIdx.x + k * 256;
-            const int ly = i >> 4, c4 = (i & 15) * 4;
-            const int gy = y0 + ly - R;
-            v[k] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-            if (i < ROWS * (TW / 4) && (unsigned)gy < (unsigned)a.H) v[k] = load4(img, gy, x0 + c4, a.W, a.vec);
-        }
-        hv = 0.f;
-        const int i = threadIdx.x;
-        if (i < ROWS * 2 * R) {
-            const int ly = i / (2 * R), k = i % (2 * R);
-            const int j = k < R ? k - R : TW + (k - R);
-            const int gy = y0 + ly - R, gx = x0 + j;
-            if ((unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W) hv = img[(long)gy * a.W + gx];
-        }
-    }
-    __device__ __forceinline__ void commit(const KindArgs& a, int x0, int y0, float* sd) const {
-#pragma unroll
-        for (int k = 0; k < NI; ++k) {
-            const int i = threadIdx.x + k * 256;
-            if (i >= ROWS * (TW / 4)) break;
-            const int ly = i >> 4, c4 = (i & 15) * 4;
-            const bool rowok = (unsigned)(y0 + ly - R) < (unsigned)a.H;
-            f32x4_t d;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) d[e] = (rowok && x0 + c4 + e < a.W) ? to_depth(a.from_inv, v[k][e]) : 0.f;
-            *(f32x4_t*)(sd + ly * LS + 4 + c4) = d;
-        }
-        const int i = threadIdx.x;
-        if (i < ROWS * 2 * R) {
-            const int ly = i / (2 * R), k = i % (2 * R);
-            const int j = k < R ? k - R : TW + (k - R);
-            const int gy = y0 + ly - R, gx = x0 + j;
-            sd[ly * LS + 4 + j] = ((unsigned)gy < (unsigned)a.H && (unsigned)gx < (unsigned)a.W) ? to_depth(a.from_inv, hv) : 0.f;
-        }
-    }
-};
-
-__device__ __forceinline__ void window(const float* sd, int ly, int c, float w[3][6]) {
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        const float* row = sd + (ly - 1 + r) * LS + 4 + c;
-        const f32x4_t m = *(const f32x4_t*)row;
-        w[r][0] = row[-1]; w[r][1] = m[0]; w[r][2] = m[1]; w[r][3] = m[2]; w[r][4] = m[3]; w[r][5] = row[4];
-    }
-}
-// Sobel responses of pixel k of the window (kernels of grad_loss.py:20-31)
-__device__ __forceinline__ void sobel4(const float w[3][6], int k, float& sh, float& sv, float& srl, float& slr) {
-    const float n0 = w[0][k], n1 = w[0][k + 1], n2 = w[0][k + 2], n3 = w[1][k], n5 = w[1][k + 2], n6 = w[2][k], n7 = w[2][k + 1], n8 = w[2][k + 2];
-    sh = (n2 - n0) + 2.f * (n5 - n3) + (n8 - n6);
-    sv = (n6 - n0) + 2.f * (n7 - n1) + (n8 - n2);
-    srl = (n1 - n3) + 2.f * (n2 - n6) + (n5 - n7);
-    slr = (n5 - n1) + 2.f * (n8 - n0) + (n7 - n3);
-}
-__device__ __forceinline__ float wave_sum_dpp(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));     // quad_perm [1,0,3,2]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));     // quad_perm [2,3,0,1]
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));    // row_half_mirror
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));    // row_mirror
-    const unsigned u = __builtin_bit_cast(unsigned, v);
-    auto r16 = __builtin_amdgcn_permlane16_swap(u, u, false, false);
-    v = __builtin_bit_cast(float, (unsigned)r16[0]) + __builtin_bit_cast(float, (unsigned)r16[1]);
-    const unsigned w = __builtin_bit_cast(unsigned, v);
-    auto r32 = __builtin_amdgcn_permlane32_swap(w, w, false, false);
-    return __builtin_bit_cast(float, (unsigned)r32[0]) + __builtin_bit_cast(float, (unsigned)r32[1]);
-}
 
 // ---- 15 x 15 box alpha (attention_loss.py:27-31) ------------------------------------------------------------------------------------
 // alpha on tile rows -AH .. TH+AH-1, columns -AH .. TW+AH-1 -> alpha[(ly + AH) * ACOLS + j + AH].  lab: ROWS x COLS floats (the alpha plane
@@ -278,15 +171,12 @@ template <typename V> __device__ void finalize(const KindArgs& a, const V& R) {
     *a.loss = (float)((double)a.weight * (base + dice));
 }
 struct LdsView { const double* l; __device__ __forceinline__ double operator()(long i) const { return l[i]; } };
-struct MemView {
-    const double* g;
-    __device__ __forceinline__ double operator()(long i) const { return __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-};
+struct MemView { const double* g; __device__ __forceinline__ double operator()(long i) const { return handoff::read(g + i); } };
 
 // workgroup sums -> record -> sample sums -> loss (sd: >= 256 doubles of dead LDS)
 __device__ void forward_tail(const KindArgs& a, int b, float acc[NP], double* sd, int sd_elems, float (*sred)[NP], int* s_last_p) {
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    volatile int& s_last = *s_last_p;
+    volatile int* s_last = s_last_p;                               // handoff::arrive broadcasts through it
 #pragma unroll
     for (int i = 0; i < NP; ++i) {
         const float s = wave_sum_dpp(acc[i]);
@@ -294,21 +184,11 @@ __device__ void forward_tail(const KindArgs& a, int b, float acc[NP], double* sd
     }
     __syncthreads();
     if (tid < NP) {
-        // returning exchange: performed at the memory side before the ticket below is drawn
         const double v = (double)sred[0][tid] + (double)sred[1][tid] + (double)sred[2][tid] + (double)sred[3][tid];
-        const unsigned long long before = atomicExch((unsigned long long*)(a.records + (long)blockIdx.x * REC) + tid, (unsigned long long)__double_as_longlong(v));
-        asm volatile("" ::"v"(before));
+        handoff::publish(a.records + (long)blockIdx.x * REC + tid, v);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
     const int per_image = a.tiles_x * a.tiles_y;
-    if (tid == 0) {
-        if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        s_last = __hip_atomic_fetch_add(a.counter + 1 + b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(per_image - 1);
-        if (s_last && a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!handoff::arrive([&] { return a.counter + 1 + b; }, [&] { return per_image; }, a.fences, a.fences, s_last)) return;
     // last workgroup of sample b: value v = tid % 16 of records k, k + 16, ... (k = tid / 16), then the 16 part sums in order
     {
         const int v = tid & 15, k = tid >> 4;
@@ -316,7 +196,7 @@ __device__ void forward_tail(const KindArgs& a, int b, float acc[NP], double* sd
         double part = 0.0;
         if (v < NP) {
 #pragma unroll 4
-            for (int j = k; j < per_image; j += 16) part += __hip_atomic_load(rec + (long)j * REC, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            for (int j = k; j < per_image; j += 16) part += handoff::read(rec + (long)j * REC);
         }
         sd[k * 16 + v] = part;
         __syncthreads();
@@ -324,24 +204,15 @@ __device__ void forward_tail(const KindArgs& a, int b, float acc[NP], double* sd
             double tot = 0.0;
 #pragma unroll
             for (int kk = 0; kk < 16; ++kk) tot += sd[kk * 16 + tid];
-            const unsigned long long before = atomicExch((unsigned long long*)(a.results + (long)b * NP) + tid, (unsigned long long)__double_as_longlong(tot));
-            asm volatile("" ::"v"(before));
+            handoff::publish(a.results + (long)b * NP + tid, tot);
         }
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __syncthreads();
-        if (tid == 0) {
-            if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-            s_last = __hip_atomic_fetch_add(a.counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(a.B - 1);
-            if (s_last && a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        }
-        __syncthreads();
-        if (!s_last) return;
+        if (!handoff::arrive([&] { return a.counter; }, [&] { return a.B; }, a.fences, a.fences, s_last)) return;
     }
     // last sample: the sums -> LDS (one round trip for the whole workgroup), one thread does the scalar arithmetic
     const int n = a.B * NP;
     if (n <= sd_elems) {
         __syncthreads();
-        for (int i = tid; i < n; i += 256) sd[i] = __hip_atomic_load(a.results + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int i = tid; i < n; i += 256) sd[i] = handoff::read(a.results + i);
         __syncthreads();
         if (tid == 0) finalize(a, LdsView{sd});
     } else if (tid == 0) {
@@ -365,7 +236,7 @@ __global__ __launch_bounds__(256) void edge_kind_fwd_kernel(KindArgs a) {
     const bool has_mask = a.mask != nullptr, has_normal = a.normal != nullptr, is_grad = a.is_grad != 0;
 
     DepthTile<1> tile;
-    if (is_grad) tile.issue(a, b, x0, y0);
+    if (is_grad) tile.issue(a, a.vec, b, x0, y0);
     f32x4_t e4[2], n4[2], m4[2], i4[2];
     const f32x4_t z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -377,7 +248,7 @@ __global__ __launch_bounds__(256) void edge_kind_fwd_kernel(KindArgs a) {
         m4[ps] = (ok && has_mask) ? load4(a.mask, img + gy, x0 + c, a.W, a.vec) : z;
         i4[ps] = (ok && !is_grad) ? load4(a.pred, img + gy, x0 + c, a.W, a.vec) : z;
     }
-    if (is_grad) tile.commit(a, x0, y0, sd);
+    if (is_grad) tile.commit(a, a.from_inv, x0, y0, sd);
     if (BOX) box_alpha<0>(a, b, x0, y0, slab, shs);
     __syncthreads();
 
@@ -475,7 +346,7 @@ __global__ __launch_bounds__(256) void edge_kind_bwd_kernel(KindArgs a) {
     f32x4_t ge[NG], gn[NG], gm[NG];
     f32x4_t inv4[2], oe4[2], om4[2];
     if (is_grad) {
-        tile.issue(a, b, x0, y0);
+        tile.issue(a, a.vec, b, x0, y0);
 #pragma unroll
         for (int q4 = 0; q4 < NG; ++q4) {
             const int i = tid + q4 * 256;
@@ -512,7 +383,7 @@ __global__ __launch_bounds__(256) void edge_kind_bwd_kernel(KindArgs a) {
     if (BOX) box_alpha<1>(a, b, x0, y0, slab, shs);               // alpha at tile (ly, j): slab[(ly + 1) * (TW + 2) + j + 1]
     constexpr int AC = Box<1>::ACOLS;
     if (is_grad) {
-        tile.commit(a, x0, y0, sd);
+        tile.commit(a, a.from_inv, x0, y0, sd);
         __syncthreads();
 #pragma unroll
         for (int kq = 0; kq < NG; ++kq) {

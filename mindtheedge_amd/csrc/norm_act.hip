@@ -22,6 +22,7 @@
 //   argument, dv = dyh*ka - (c0 + v*c1) for the backward) and every optional input is a template flag: the
 //   backward apply kernel went from 208 to <100 VGPRs (2 -> 5 waves per SIMD), which is what an HBM stream needs.
 #include "common.hpp"
+#include "handoff.hpp"
 
 int g_mte_gn_prezeroed = 0;
 int g_mte_handoff_fences = 0;
@@ -228,26 +229,12 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(GnArgs a) {
         float tot = 0.f;
 #pragma unroll
         for (int w = 0; w < NW; ++w) tot += s_part[w * GN_GROUPS * 2 + threadIdx.x];
-        const unsigned long long before = atomicExch((unsigned long long*)part + threadIdx.x, (unsigned long long)__double_as_longlong((double)tot));
-        asm volatile("" ::"v"(before));                    // returning: the record is at the memory side once the value is back
+        handoff::publish(part + threadIdx.x, (double)tot);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        // (TAIL writes its output through this XCD's L2: a release there would also write those lines back, per workgroup -- the records are
-        //  returning exchanges, at the memory side already, so the tail keeps the relaxed ticket whatever the option says)
-        if (a.fences && !TAIL) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        const unsigned old = __hip_atomic_fetch_add(mte_gn_tickets(a.stats, a.B) + 2 * b, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        s_last = old == gridDim.x - 1;
-        if (s_last) {
-            // the last arriver puts the ticket back: a statistics buffer can be used again without being cleared (MTE_OPT_GN_PREZEROED is
-            // then an optimisation of the FIRST use, not a precondition of every use)
-            __hip_atomic_store(mte_gn_tickets(a.stats, a.B) + 2 * b, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    // TAIL writes its output through this XCD's L2: a release there would also write those lines back, per workgroup, so the tail keeps the
+    // relaxed ticket whatever the option says.  The last arriver puts the ticket back: a statistics buffer can be used again without being
+    // cleared (MTE_OPT_GN_PREZEROED is then an optimisation of the FIRST use, not a precondition of every use).
+    if (!handoff::arrive<true>([&] { return mte_gn_tickets(a.stats, a.B) + 2 * b; }, [] { return gridDim.x; }, a.fences && !TAIL, a.fences, &s_last)) return;
     // every record of sample b is in memory: NT / 32 threads per value take the slots j = k, k + NT/32, ... in order, then the
     // NT / 32 partial sums are added in order
     {
@@ -255,7 +242,7 @@ __global__ __launch_bounds__(NT) void gn_stats_kernel(GnArgs a) {
         const double* rec = mte_gn_partials(a.stats, a.B) + (long)b * slots * (GN_GROUPS * 2) + v;
         double acc = 0.0;
         for (int j = k; j < (int)gridDim.x; j += NT / 32)
-            acc += __hip_atomic_load(rec + (long)j * (GN_GROUPS * 2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            acc += handoff::read(rec + (long)j * (GN_GROUPS * 2));
         s_fin[k * 32 + v] = acc;
     }
     __syncthreads();

@@ -16,8 +16,7 @@
 // Layout: a workgroup is one (scale, CHUNK-pixel slice of the scale's [B,H,W] plane); a thread owns 4 consecutive pixels per pass
 // (16-byte prediction loads when W % 4 == 0), PASSES passes.  The ground truth is gathered at the nearest source index.
 //
-// Sums: fp32 per thread and per wave, fp64 per workgroup record.  The last workgroup of the launch to arrive (agent-scope ticket, records
-// written with returning vector atomics and read with agent-scope atomic loads, fences on MTE_OPT_HANDOFF_FENCES, as in edge_loss_kinds.hip) reduces
+// Sums: fp32 per thread and per wave, fp64 per workgroup record.  The last workgroup of the launch to arrive (handoff.hpp) reduces
 // the records of each scale in a fixed order and writes the loss, the per-scale values and the backward coefficients.  No floating-point
 // atomics and no host sync; each forward call clears its tickets with a fill kernel, so the launches can be captured in a graph and the
 // results are bit-reproducible.  BerHu takes two launches: A gives N, sum D and max(x - y), its last workgroup writes c; B reads c from
@@ -26,6 +25,7 @@
 // The nearest upsample (integer ratios only) writes the full-resolution maps; its backward gathers each r x r block in row-major order, as
 // torch's CPU backward accumulates it, with no atomics.  One launch covers every map.
 #include "common.hpp"
+#include "handoff.hpp"
 
 namespace {
 
@@ -51,7 +51,7 @@ struct SupArgs {
     const float* depth;                  // metric depth [B,1,Hd,Wd]
     int Hd, Wd, B, n, method, sparse;
     int pass;                            // 0: the loss (BerHu: launch A), 1: BerHu launch B
-    int fences;                          // mte_set_option(MTE_OPT_HANDOFF_FENCES): agent-scope release / acquire around the ticket
+    int fences;                          // MTE_OPT_HANDOFF_FENCES (handoff.hpp)
     unsigned* ticket;                    // this launch's arrival ticket (zeroed by the launcher)
     double* res;                         // [MAXS][RES] BerHu: launch A -> launch B
     double* records;                     // [blocks][REC]
@@ -212,19 +212,9 @@ __global__ __launch_bounds__(NT) void sup_fwd_kernel(SupArgs a) {
         double v;
         if (tid == 3) v = (double)fmaxf(fmaxf(sred[0][3], sred[1][3]), fmaxf(sred[2][3], sred[3][3]));
         else v = (double)sred[0][tid] + (double)sred[1][tid] + (double)sred[2][tid] + (double)sred[3][tid];
-        // returning exchange: performed at the memory side before the ticket below is drawn
-        const unsigned long long before = atomicExch((unsigned long long*)(a.records + (long)blockIdx.x * REC) + tid, (unsigned long long)__double_as_longlong(v));
-        asm volatile("" ::"v"(before));
+        handoff::publish(a.records + (long)blockIdx.x * REC + tid, v);
     }
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) {
-        if (a.fences) { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-        s_last = __hip_atomic_fetch_add(a.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (unsigned)(a.first[a.n] - 1);
-        if (s_last && a.fences) { __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent"); asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-    }
-    __syncthreads();
-    if (!s_last) return;
+    if (!handoff::arrive([&] { return a.ticket; }, [&] { return a.first[a.n]; }, a.fences, a.fences, &s_last)) return;
 
     // last workgroup: per scale, thread t adds records t, t + 256, ... then a fixed-order tree over the 256 partials
     for (int sc = 0; sc < a.n; ++sc) {
@@ -232,8 +222,8 @@ __global__ __launch_bounds__(NT) void sup_fwd_kernel(SupArgs a) {
         for (int j = a.first[sc] + tid; j < a.first[sc + 1]; j += NT) {
             const double* rec = a.records + (long)j * REC;
 #pragma unroll
-            for (int v = 0; v < 3; ++v) part[v] += __hip_atomic_load(rec + v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            part[3] = fmax(part[3], __hip_atomic_load(rec + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+            for (int v = 0; v < 3; ++v) part[v] += handoff::read(rec + v);
+            part[3] = fmax(part[3], handoff::read(rec + 3));
         }
 #pragma unroll
         for (int v = 0; v < REC; ++v) sd[v][tid] = part[v];
