@@ -519,7 +519,8 @@ int mte_color_jitter_u8_to_f32(const unsigned char* in, int B, int H, int W, con
  *      1 = 6 slots, 3 = always 3 slots x 2 workgroups, 4 = always 4 slots
  *   19 implicit GEMM: two-workgroup 256x128 variant beside the
  *      weight-gradient stream for launches with at most this many K-steps and >= 512 tiles (72 [default], 0 = solo launches only)
- *   17 implicit GEMM main-loop ablation (tools/igemm_ablate.py): leave out 1 MFMAs | 2 in-loop LDS-DMA | 4 fragment reads; results are garbage */
+ *   17 implicit GEMM main-loop ablation (tools/igemm_ablate.py): leave out 1 MFMAs | 2 in-loop LDS-DMA | 4 fragment reads; results are garbage
+ *   33 every implicit-GEMM key (0, 6, 7, 15, 17, 19, 21, 23, 24, 28, 29, 32: IgemmKnobs, csrc/conv_plan.hpp) back to its default; the value is ignored */
 int mte_debug_set(int key, int value);
 #endif /* MTE_DEV */
 

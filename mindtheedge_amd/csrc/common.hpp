@@ -205,4 +205,9 @@ static inline int mte_check_launch() {
     if (e != hipSuccess) fprintf(stderr, "[libmte_hip] launch failed: %s (%s)\n", hipGetErrorName(e), hipGetErrorString(e));
     return e == hipSuccess ? MTE_OK : MTE_ERR_LAUNCH;
 }
+// Dynamic LDS beyond the 64 KiB a kernel may use unasked: granted once per kernel (the function-local static), before its first launch with `bytes`.
+template <auto Kernel> int mte_allow_lds(int bytes) {
+    static const bool ok = hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    return ok ? MTE_OK : MTE_ERR_LAUNCH;
+}
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }

@@ -1,6 +1,7 @@
 // Argument block of the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm8.hip).
 #pragma once
 #include "common.hpp"
+#include "conv_plan.hpp"
 
 struct ConvArgs {
     const void* x; long ldx;        // input pixels, elements per pixel (>= Cin_p)
@@ -31,6 +32,6 @@ struct ConvArgs {
     int unshuffle_c;
 };
 
-// conv_igemm8.hip: the 8-phase 256-row tile kernels (bf16, buffer-descriptor LDS-DMA).  bn = 256 or 128 output columns per tile.
-// Returns MTE_ERR_UNSUPPORTED when the shape is outside what the kernel covers (the caller then takes the older tile forms).
-__attribute__((visibility("hidden"))) int igemm8_launch(ConvArgs a, int bn, hipStream_t st);
+// conv_igemm8.hip: the 8-phase 256-row tile kernels (bf16, buffer-descriptor LDS-DMA).  Launches the instance the plan names (form P8_256x256 / P8_256x128,
+// kslice, one) with the plan's grid and LDS, after its LDS opt-in; decides nothing, the caller checks the launch.  a.splits / a.kslice are the plan's.
+__attribute__((visibility("hidden"))) int igemm8_launch(const IgemmPlan& p, const ConvArgs& a, hipStream_t st);

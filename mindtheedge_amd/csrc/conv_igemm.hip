@@ -61,9 +61,7 @@ template <> struct Mma<float> {
 // 32x32x16, but MFMA-dense loops on random data hold a higher clock with it (MI355X_MICROARCH.md, DVFS item 7: 1.12-1.15x the FLOP/s
 // at equal cycles per FLOP).  One K-step (64 B per row) is exactly one 16x16x32 reduction: lane (r16 = lane & 15, q = lane >> 4) reads
 // the 16-byte chunk q of tile row r16 -- the same LDS bytes per MFMA FLOP as before.  0 = the 32x32x16 form (same-box A/B builds).
-#ifndef MTE_IGEMM_MFMA16
-#define MTE_IGEMM_MFMA16 1
-#endif
+// (the default, 1, is set in conv_plan.hpp: the dispatch rule reads the macro too)
 #if MTE_IGEMM_MFMA16
 // chunk c of row r sits at slot c ^ ((r >> 1) & 3): conflict-free for the 16-row fragment reads (every ds_read_b128 lane group
 // {0-3, 12-15, 20-27}, ... meets 16 distinct 16-byte slots; the (r >> 2) form of the 32-row reads is 2-way conflicted here)
@@ -661,7 +659,6 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_igemm_kernel(ConvArgs
     }
 }
 
-int g_igemm_dma = 1;                                 // development knob (mte_debug_set(0, v))
 
 // y = T(sum_s ws[s] + bias) after a split-K launch: the slabs are added in split order (fixed), rounded once
 template <typename T>
@@ -676,203 +673,102 @@ __global__ void splitk_finish_kernel(const float* __restrict__ ws, int splits, c
     }
 }
 
-// split-K factor for small-M / huge-K layers (pack5.conv: 120 tiles for 256 CUs); 1 = no split
-inline int choose_splits(long tiles, int ksteps, long M, int N, long ws_elems, int nthr = 256) {
-    const long want = 768L * 256 / nthr;               // ~3 four-wave workgroups per CU, or their equivalent in larger ones
-    if (tiles >= want / 2 || ws_elems < M * N || N % 4 != 0) return 1;
-    long s = (want + tiles - 1) / tiles;
-    const long max_s = ksteps / 16;                    // keep >= 16 K-steps (1 KiB of K per row) per split
-    if (s > max_s) s = max_s;
-    if (s > ws_elems / (M * N)) s = ws_elems / (M * N);   // one [M][N] slab per split
-    return (int)(s < 1 ? 1 : s);
+IgemmKnobs g_igemm_knobs;                            // development knobs of plan_igemm (conv_plan.hpp): mte_debug_set writes them, nothing else does
+
+template <auto Kernel> int launch_instance(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    if (p.lds_optin && mte_allow_lds<Kernel>(p.lds_bytes) != MTE_OK) return MTE_ERR_LAUNCH;
+    hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, a);
+    return MTE_OK;
 }
 
-int g_igemm_pair_ksteps = 72;                        // development knob (mte_debug_set(19, v))
-#ifdef MTE_DEV
-int g_igemm_ablate = 0;                              // development knob (mte_debug_set(17, v)): main-loop ablation, see ABL
-#endif
-int g_igemm_ring6 = 0;                               // development knob (mte_debug_set(15, v)) for the 8-wave 256 x 128 tile: 1 = 6-slot ring, 3 = 3-slot ring with two workgroups per CU
+// one number per (tile form, element type, loader, ring): what the switch of launch_plan is over
+constexpr int igemm_instance(IgemmForm f, int elem_size, int loader, int ring = 4) { return (((int)f * 2 + (elem_size == 4)) * 4 + loader) * 8 + ring; }
 
-template <typename T, int WM, int WN, int TM, int TN>
-int launch_igemm(ConvArgs a, long ws_elems, hipStream_t st) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32, NTHR = WM * WN * 64;
-    const long tiles = ((a.M + BM - 1) / BM) * ((a.N + BN - 1) / BN);
-    const int ksteps = (a.KH * a.KW * (a.Cin_p / Elem<T>::PER16) + 3) / 4;
-    a.splits = (a.ws && !a.out_f32 && !a.rows) ? choose_splits(tiles, ksteps, a.M, a.N, ws_elems, NTHR) : 1;
-    if (a.unshuffle_c && (a.splits != 1 || a.out_f32 || a.rows || sizeof(T) != 2 || BN % 32 != 0 || (BN * 4) % NTHR != 0 || !g_igemm_dma)) return MTE_ERR_UNSUPPORTED;
-    if constexpr ((BN * 4) % NTHR == 0) {
-        if (g_igemm_dma) {
-            const size_t lds4 = 4 * (BM + BN) * 64;
-            const long es = (long)sizeof(T);
-            const bool fast = g_igemm_dma == 1 && a.Cin_p % (4 * Elem<T>::PER16) == 0 &&
-                              ((a.M - 1) * a.ldx + a.Cin_p) * es < 0x7ff00000L && (long)a.N * a.KH * a.KW * a.Cin_p * es < 0x7ff00000L;
+// the main-loop ablation arms (IgemmPlan.ablate; planned only in the build that has them)
 #if defined(MTE_DEV) && !MTE_IGEMM_MFMA16
-            if constexpr (sizeof(T) == 2 && ((BM == 256 && BN == 128) || (BM == 128 && BN == 128) || (BM == 256 && BN == 256))) {
-                if (fast && g_igemm_ablate) {
-                    const dim3 g((unsigned)(tiles * a.splits)), b(NTHR);
-                    switch (g_igemm_ablate) {
-                    case 1: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 1>), g, b, lds4, st, a); break;
-                    case 2: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 2>), g, b, lds4, st, a); break;
-                    case 3: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 3>), g, b, lds4, st, a); break;
-                    case 4: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 4>), g, b, lds4, st, a); break;
-                    case 5: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 5>), g, b, lds4, st, a); break;
-                    case 6: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 6>), g, b, lds4, st, a); break;
-                    default: hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 4, 1, 7>), g, b, lds4, st, a); break;
-                    }
-                    goto launched;
-                }
-            }
-#endif
-            if constexpr (sizeof(T) == 2 && BM == 256 && BN == 128) {
-                // two 74 KB workgroups per CU (3-slot ring): always for solo launches; beside the weight-gradient stream only for short
-                // reductions over several rounds of tiles, where the prologue / epilogue share is largest (same-box step 30.46 -> 30.30 ms;
-                // for every launch it costs the step 0.2 ms)
-                const bool pair = a.solo || (ksteps <= g_igemm_pair_ksteps && tiles >= 512);
-                if (fast && (g_igemm_ring6 == 3 || (g_igemm_ring6 == 0 && pair))) {
-                    constexpr size_t lds3 = 3 * (BM + BN) * 64;
-                    static bool attr3 = false;
-                    if (!attr3) {
-                        if (hipFuncSetAttribute((const void*)conv_igemm_kernel<T, WM, WN, TM, TN, 2, 3, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3) != hipSuccess) return MTE_ERR_LAUNCH;
-                        attr3 = true;
-                    }
-                    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 3, 4>), dim3((unsigned)(tiles * a.splits)), dim3(NTHR), lds3, st, a);
-                    goto launched;
-                }
-                if (fast && g_igemm_ring6 == 1) {
-                    constexpr size_t lds6 = 6 * (BM + BN) * 64;
-                    static bool attr = false;
-                    if (!attr) {
-                        if (hipFuncSetAttribute((const void*)conv_igemm_kernel<T, WM, WN, TM, TN, 2, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds6) != hipSuccess) return MTE_ERR_LAUNCH;
-                        attr = true;
-                    }
-                    hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2, 6>), dim3((unsigned)(tiles * a.splits)), dim3(NTHR), lds6, st, a);
-                    goto launched;
-                }
-            }
-            if (fast) hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 2>), dim3((unsigned)(tiles * a.splits)), dim3(NTHR), lds4, st, a);
-            else hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 1>), dim3((unsigned)(tiles * a.splits)), dim3(NTHR), lds4, st, a);
-            goto launched;
-        }
+template <int WM, int WN, int TM, int TN> int launch_ablated_tile(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    switch (p.ablate) {
+    case 1: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 1>>(p, a, st);
+    case 2: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 2>>(p, a, st);
+    case 3: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 3>>(p, a, st);
+    case 4: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 4>>(p, a, st);
+    case 5: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 5>>(p, a, st);
+    case 6: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 6>>(p, a, st);
+    default: return launch_instance<conv_igemm_kernel<bf16_t, WM, WN, TM, TN, 2, 4, 1, 7>>(p, a, st);
     }
-    if constexpr (NTHR == 256)
-        hipLaunchKernelGGL((conv_igemm_kernel<T, WM, WN, TM, TN, 0>), dim3((unsigned)(tiles * a.splits)), dim3(256), 2 * (BM + BN) * 64, st, a);
-    else return MTE_ERR_UNSUPPORTED;
-launched:
-    if (a.splits > 1) {
-        long g = (a.M * a.N / 4 + 255) / 256; if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3((unsigned)g), dim3(256), 0, st, a.ws, a.splits, a.bias, (T*)a.y, a.ldy, a.M, a.N, a.accum);
+}
+int launch_ablated(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    switch (p.form) {
+    case IgemmForm::T256x128: return launch_ablated_tile<4, 2, 2, 2>(p, a, st);
+    case IgemmForm::T128x128: return launch_ablated_tile<2, 2, 2, 2>(p, a, st);
+    case IgemmForm::T256x256_PP: return launch_ablated_tile<2, 4, 4, 2>(p, a, st);
+    case IgemmForm::T256x256_W16: return launch_ablated_tile<4, 4, 2, 2>(p, a, st);
+    default: return MTE_ERR_UNSUPPORTED;
+    }
+}
+#else
+int launch_ablated(const IgemmPlan&, const ConvArgs&, hipStream_t) { return MTE_ERR_UNSUPPORTED; }
+#endif
+
+// Launches what plan_igemm chose: the template instance, its LDS opt-in, the launch, the split-K finish, the launch check.  Every instance of both kernels
+// that the library holds is named here once (some loader / tile pairs are built but never planned: the larger tiles are only chosen where LD = 2 applies).
+int launch_plan(const IgemmPlan& p, ConvArgs a, hipStream_t st) {
+    using F = IgemmForm;
+    if (p.rc != MTE_OK) return p.rc;
+    a.splits = p.splits;
+    a.kslice = p.kslice;
+    int rc = MTE_ERR_UNSUPPORTED;
+#define MTE_IGEMM_CASE(FORM, T, WM, WN, TM, TN, ...) \
+    case igemm_instance(FORM, sizeof(T), __VA_ARGS__): rc = launch_instance<conv_igemm_kernel<T, WM, WN, TM, TN, __VA_ARGS__>>(p, a, st); break
+    if (p.form == F::P8_256x256 || p.form == F::P8_256x128) rc = igemm8_launch(p, a, st);      // (the same steps over its own instances)
+    else if (p.ablate) rc = launch_ablated(p, a, st);
+    else switch (igemm_instance(p.form, p.elem_size, p.loader, p.ring)) {
+    MTE_IGEMM_CASE(F::T128x32, bf16_t, 4, 1, 1, 1, 0);
+    MTE_IGEMM_CASE(F::T128x32_W2, bf16_t, 2, 1, 2, 1, 2);
+    MTE_IGEMM_CASE(F::T128x32_W2, bf16_t, 2, 1, 2, 1, 1);
+    MTE_IGEMM_CASE(F::T128x64, bf16_t, 2, 2, 2, 1, 2);
+    MTE_IGEMM_CASE(F::T128x64, bf16_t, 2, 2, 2, 1, 1);
+    MTE_IGEMM_CASE(F::T128x64, bf16_t, 2, 2, 2, 1, 0);
+    MTE_IGEMM_CASE(F::T128x128, bf16_t, 2, 2, 2, 2, 2);
+    MTE_IGEMM_CASE(F::T128x128, bf16_t, 2, 2, 2, 2, 1);
+    MTE_IGEMM_CASE(F::T128x128, bf16_t, 2, 2, 2, 2, 0);
+    MTE_IGEMM_CASE(F::T192x96, bf16_t, 2, 3, 3, 1, 2);
+    MTE_IGEMM_CASE(F::T192x96, bf16_t, 2, 3, 3, 1, 1);
+    MTE_IGEMM_CASE(F::T256x128, bf16_t, 4, 2, 2, 2, 2);
+    MTE_IGEMM_CASE(F::T256x128, bf16_t, 4, 2, 2, 2, 1);
+    MTE_IGEMM_CASE(F::T256x128, bf16_t, 4, 2, 2, 2, 2, 6);
+    case igemm_instance(F::T256x128, 2, 2, 3): rc = launch_instance<conv_igemm_kernel<bf16_t, 4, 2, 2, 2, 2, 3, 4>>(p, a, st); break;   // (two workgroups per CU)
+    MTE_IGEMM_CASE(F::T256x256_PP, bf16_t, 2, 4, 4, 2, 2);
+    MTE_IGEMM_CASE(F::T256x256_PP, bf16_t, 2, 4, 4, 2, 1);
+    MTE_IGEMM_CASE(F::T256x256_W16, bf16_t, 4, 4, 2, 2, 2);
+    MTE_IGEMM_CASE(F::T256x256_W16, bf16_t, 4, 4, 2, 2, 1);
+    MTE_IGEMM_CASE(F::T128x32, float, 4, 1, 1, 1, 0);
+    MTE_IGEMM_CASE(F::T128x64, float, 2, 2, 2, 1, 2);
+    MTE_IGEMM_CASE(F::T128x64, float, 2, 2, 2, 1, 1);
+    MTE_IGEMM_CASE(F::T128x64, float, 2, 2, 2, 1, 0);
+    MTE_IGEMM_CASE(F::T128x128, float, 2, 2, 2, 2, 2);
+    MTE_IGEMM_CASE(F::T128x128, float, 2, 2, 2, 2, 1);
+    MTE_IGEMM_CASE(F::T128x128, float, 2, 2, 2, 2, 0);
+    }
+#undef MTE_IGEMM_CASE
+    if (rc != MTE_OK) return rc;
+    if (p.finish) {
+        if (p.elem_size == 2) hipLaunchKernelGGL(splitk_finish_kernel<bf16_t>, dim3(p.finish_grid), dim3(256), 0, st, a.ws, a.splits, a.bias, (bf16_t*)a.y, a.ldy, a.M, a.N, a.accum);
+        else hipLaunchKernelGGL(splitk_finish_kernel<float>, dim3(p.finish_grid), dim3(256), 0, st, a.ws, a.splits, a.bias, (float*)a.y, a.ldy, a.M, a.N, a.accum);
     }
     return mte_check_launch();
 }
 
-int g_igemm_big_min_tiles = 224;
-// Default 51 = 19 | 32: TAP-major.  The slice-major order of round 5 (ConvArgs.kslice) cuts the implicit GEMM's fetches beyond L2 (the nine tap sweeps
-// of a 64-channel slice re-use the lines of the first), but those fetches were Infinity-Cache hits, not HBM reads: same box, the training step takes
-// 24.80 ms with it and 24.77 ms without, and in isolation the kernels are 5 % SLOWER (a tap change, i.e. new lane offsets, every K-tile): 6.74 against
-// 6.43 ms over the step's launches (profiles/r05_igemm8_korder.txt).  It stays selectable: knob 23 without bit 5, or -DMTE_IGEMM8_DEFAULT=19.
-#ifndef MTE_IGEMM8_DEFAULT
-#define MTE_IGEMM8_DEFAULT 51
+#ifdef MTE_DEV
+constexpr bool kDevBuild = true;
+#else
+constexpr bool kDevBuild = false;
 #endif
-int g_igemm8 = MTE_IGEMM8_DEFAULT;                                   // development knob (mte_debug_set(23, v)): bit 0 = 8-phase 256 x 256 kernel, bit 1 = its 256 x 128 form, bit 2 every eligible launch, bit 5 (32) tap-major K order (the default; without it: slice-major where Cin_p % 64 == 0); bits 3 / 4 belonged to the tile-walking form, removed in round 5
-int g_igemm_n32_dma = 1;                              // development knob (mte_debug_set(32, v)): N <= 32 on the two-wave LDS-DMA form
-int g_igemm8_split_bn128 = 64;                        // development knob (mte_debug_set(29, v)): see the split-K rule of the 8-phase kernels
-int g_igemm8_min_tiles = 200;                        // development knob (mte_debug_set(24, v))
-int g_igemm_pp = 1;                                  // development knob (mte_debug_set(21, v)): 0 = the 16-wave one-barrier loop on the 256 x 256 tile
-int g_igemm_big = 3;                                 // development knob (mte_debug_set(6, v)): 0 128x128 only, 1 + 256x128, 2 + 256x256, 3 + 192x96
 
-template <typename T> int dispatch_igemm(const ConvArgs& a, long ws_elems, hipStream_t st) {
-    if constexpr (sizeof(T) == 2) {
-        // 256 x 128 tile, 8 waves: 24 KB of operands per K-step feed twice the MFMA work of a 128 x 128 tile (16 KB).  The
-        // 4-wave kernel runs at ~14 TB/s of L2->LDS traffic with three stages in flight -- the latency-bandwidth product,
-        // not the MFMA pipe, bounds it -- so fewer bytes per flop is the lever.  Needs the buffer-DMA loader and enough
-        // tiles to cover the CUs.
-        const long tiles_big = ((a.M + 255) / 256) * ((a.N + 127) / 128);
-        const bool dma_ok = g_igemm_dma == 1 && a.Cin_p % 32 == 0 && ((a.M - 1) * a.ldx + a.Cin_p) * 2 < 0x7ff00000L &&
-                            (long)a.N * a.KH * a.KW * a.Cin_p * 2 < 0x7ff00000L;
-        // (odd widths -- 72 / 104 / 200 input channels of the decoder concats as data-gradient N -- take the tile that covers
-        //  them in ONE column block: the padded columns cost the same MFMA work as two narrower blocks, A is read once)
-        const long n256 = (a.N + 255) / 256;
-        const long t256 = ((a.M + 255) / 256) * n256;
-        const int ksteps = a.KH * a.KW * (a.Cin_p / 32);
-        // few tiles but a huge reduction (pack4/pack5.conv: K = 9 x 4096 / 8192): the big tiles keep their bytes-per-flop
-        // advantage when the K range is split over workgroups (fp32 atomics into the workspace, then the finish kernel)
-        const bool can_split = a.ws && ws_elems >= 2 * a.M * a.N && a.N % 4 == 0;
-        long smax = can_split ? ws_elems / (a.M * a.N) : 1;                    // one [M][N] slab per split
-        if (smax > 8) smax = 8;
-        const long reach256 = t256 * (can_split ? (ksteps / 16 < smax ? (ksteps / 16 > 0 ? ksteps / 16 : 1) : smax) : 1);
-        // ---- round 4: the 8-phase kernels (conv_igemm8.hip) take every launch the 256-row tiles took
-        if (g_igemm8 && dma_ok && !a.out_f32 && !a.rows && a.N > 64 && !a.unshuffle_c) {
-            const bool wide = a.N > 128 && (a.N % 256 == 0 || a.N % 256 > 128);
-            const int nkt = (ksteps + 1) / 2;                                                      // K-tiles of 64
-            int bn = 0, splits = 1;
-            // Same-box A/B against the older tile forms over the training step's shapes (tools/igemm8_check.py bench; profiles/r04_igemm8_ab.txt):
-            // one workgroup per CU, so a launch of SEVERAL rounds of tiles pays prologue + epilogue (~ 6 K-tiles' worth) per round, where the
-            // 256 x 128 kernel it replaces runs two workgroups per CU: short reductions over many tiles stay with the older forms.
-            if (g_igemm8 & 4) {                                                                    // (development: every eligible launch)
-                if (wide && t256 >= g_igemm8_min_tiles) bn = 256;
-                else if (tiles_big >= g_igemm8_min_tiles) bn = 128;
-            } else if (wide && (g_igemm8 & 1) && t256 >= g_igemm8_min_tiles) {
-                if (nkt >= (t256 <= 256 ? 18 : 36)) bn = 256;
-            } else if ((g_igemm8 & 2) && tiles_big >= g_igemm8_min_tiles && tiles_big <= 256 && nkt >= 36) bn = 128;
-            if (!bn && wide && (g_igemm8 & 1) && can_split && t256 < 128 && ksteps >= 32) {        // few tiles, long reduction: split K
-                bn = 256;
-                long tsp = t256;
-                // Round 6: very few tiles AND a short reduction (the 512-channel 12x40 / 24x80 layers: K = 4608) -> 256 x 128 tiles with half the K splits.  Such a
-                // launch is dominated by its fp32 slabs (8 x 7.9 MB written and read back for a 3.9 MB result at 12x40); half the slabs: 41.7 -> 35.2 us forward,
-                // 39.7 -> 33.4 data gradient at 512 -> 512 @12x40, 55.9 -> 52.4 at 512 -> 256 @24x80.  With a long reduction (pack4 / pack5.conv: K = 36,864 /
-                // 73,728) the slabs do not matter and the narrower tile loses 15 % (265 -> 305 us): profiles/r06_lowres_split.txt.  Knob 29 = tile bound (0: off).
-                if (t256 <= g_igemm8_split_bn128 && ksteps <= 288) { bn = 128; tsp = tiles_big; }
-                long sp = 256 / tsp;                                                               // one round of workgroups
-                if (sp > smax) sp = smax;
-                if (sp > ksteps / 16) sp = ksteps / 16;                                            // >= 8 K-tiles per split
-                const int per = (int)((ksteps + sp - 1) / (sp < 1 ? 1 : sp));
-                splits = (ksteps + per - 1) / per;                                                 // (no empty split)
-            }
-            if (bn) {
-                ConvArgs b = a;
-                b.splits = splits;
-                // round 5: 64-channel slices outer, taps inner where asked for and the channels allow it (ConvArgs.kslice; knob 23 bit 5 = tap-major, the order of
-                // every other tile form and the default -- see g_igemm8).  The tile-walking (persistent) form of round 4 is gone: it was 15-20 % slower per
-                // launch than one workgroup per tile and no launch used it.
-                b.kslice = (!(g_igemm8 & 32) && a.Cin_p % 64 == 0) ? 1 : 0;
-                const int rc = igemm8_launch(b, bn, st);
-                if (rc == MTE_OK) {
-                    if (splits > 1) {
-                        long g = (a.M * a.N / 4 + 255) / 256; if (g > 4096) g = 4096;
-                        hipLaunchKernelGGL(splitk_finish_kernel<T>, dim3((unsigned)g), dim3(256), 0, st, a.ws, splits, a.bias, (T*)a.y, a.ldy, a.M, a.N, a.accum);
-                    }
-                    return mte_check_launch();
-                }
-                if (rc != MTE_ERR_UNSUPPORTED) return rc;
-            }
-        }
-        if (g_igemm_big >= 2 && dma_ok && !a.out_f32 && a.N > 128 && (a.N % 256 == 0 || a.N % 256 > 128) &&
-            (t256 >= g_igemm_big_min_tiles || (can_split && t256 < 96 && reach256 >= 160))) {   // (96: below it choose_splits does split)
-            // enough tiles without a K split: 8 waves of 128 x 64 in the ping-pong loop (same-box A/B per layer: 256 -> 256 3x3 @48x160
-            // 70.2 -> 66 us, 384 -> 256 106 -> 95-101, 5x5 64 -> 256 @96x320 226 -> 212, 128 -> 512 @48x160 203 -> 189); the split-K
-            // launches (few tiles, short per-split reductions) lose with it and keep the 16-wave one-barrier loop
-            if (g_igemm_pp && t256 >= g_igemm_big_min_tiles) return launch_igemm<T, 2, 4, 4, 2>(a, 0, st);
-            return launch_igemm<T, 4, 4, 2, 2>(a, t256 >= g_igemm_big_min_tiles ? 0 : ws_elems, st);   // 256 x 256, 16 waves
-        }
-        // 65..96 columns (the 72-channel decoder concat as data-gradient N): a 192 x 96 tile of 6 waves wastes a quarter of
-        // the MFMA work instead of the 44 % a 128-wide tile does
-        if (g_igemm_big >= 3 && dma_ok && !a.out_f32 && a.N > 64 && a.N <= 96 && ((a.M + 191) / 192) >= g_igemm_big_min_tiles)
-            return launch_igemm<T, 2, 3, 3, 1>(a, 0, st);
-        if (g_igemm_big && dma_ok && !a.out_f32 && a.N > 64 && tiles_big >= g_igemm_big_min_tiles)
-            return launch_igemm<T, 4, 2, 2, 2>(a, 0, st);
-    }
-    if (a.N <= 32) {
-        // round 6: two waves of 64 x 32 where the LDS-DMA loader applies (its B stage needs (BN * 4) % threads == 0, which the four-wave 128 x 32 form misses: that
-        // one stages through registers) -- the 32-output band convolutions of the folded pack layers (K = 25 x 512)
-        if constexpr (sizeof(T) == 2) {
-            if (g_igemm_n32_dma && g_igemm_dma == 1 && a.Cin_p % 32 == 0 && !a.out_f32 && ((a.M - 1) * a.ldx + a.Cin_p) * 2 < 0x7ff00000L &&
-                (long)a.N * a.KH * a.KW * a.Cin_p * 2 < 0x7ff00000L)
-                return launch_igemm<T, 2, 1, 2, 1>(a, ws_elems, st);
-        }
-        return launch_igemm<T, 4, 1, 1, 1>(a, ws_elems, st);       // 128 x 32
-    }
-    if (a.N <= 64) return launch_igemm<T, 2, 2, 2, 1>(a, ws_elems, st);        // 128 x 64
-    return launch_igemm<T, 2, 2, 2, 2>(a, ws_elems, st);                      // 128 x 128
+// the three entry points: fill the problem, plan, launch
+int plan_and_launch(const ConvArgs& a, int elem_size, long ws_elems, hipStream_t st) {
+    const IgemmProblem p{elem_size, a.M, a.N, a.Cin_p, a.KH, a.KW, a.ldx, a.out_f32, a.rows != nullptr, a.unshuffle_c, a.solo, a.ws != nullptr, ws_elems};
+    return launch_plan(plan_igemm(p, g_igemm_knobs, kDevBuild), a, st);
 }
 
 // =====================================================================================================
@@ -1729,41 +1625,29 @@ __global__ __launch_bounds__(256) void colsum_kernel(const T* __restrict__ y, lo
 extern "C" {
 
 #ifdef MTE_DEV
-// development knobs (libmte_hip_dev.so only, -DMTE_DEV): key 0 = igemm tile loader (1 = LDS-DMA ring with buffer descriptors where possible, 2 = pointer DMA only,
-// 0 = register staging); key 1 = conv3d pack stencils
+// development knobs (libmte_hip_dev.so only, -DMTE_DEV): the implicit-GEMM keys are IgemmKnobs (conv_plan.hpp); key 1 = conv3d pack stencils
 // (1 = LDS-tiled, 0 = gather).  Not part of the product contract.
 extern "C" int mtei_set_pack3d_lds(int value);
 extern "C" int mtei_set_gn(int which, int value);
 extern "C" int mtei_set_patch_tall(int v);
 extern "C" int mtei_set_tap_wgrad(int v);            // tap_wgrad.hip
 extern "C" int mtei_set_head_mfma(int v);
-extern int g_wgrad9, g_wgrad9_wgs, g_igemm8_one;
+extern int g_wgrad9, g_wgrad9_wgs;
 int mte_debug_set(int key, int value) {
+    if (igemm_knob_set(g_igemm_knobs, key, value)) return MTE_OK;      // keys 0, 6, 7, 15, 17, 19, 21, 23, 24, 28, 29, 32; 33 = all of them back to their defaults
     if (key == 26) { g_wgrad9 = value; return MTE_OK; }
     if (key == 27) { g_wgrad9_wgs = value; return MTE_OK; }
-    if (key == 28) { g_igemm8_one = value; return MTE_OK; }
     if (key == 30) return mtei_set_head_mfma(value);
     if (key == 31) return mtei_set_tap_wgrad(value);
-    if (key == 0) { g_igemm_dma = value; return MTE_OK; }
     if (key == 1) return mtei_set_pack3d_lds(value);
     if (key == 2 || key == 3) return mtei_set_gn(key - 2, value);
     if (key == 13) return mtei_set_gn(2, value);
-    if (key == 15) { g_igemm_ring6 = value; return MTE_OK; }
-    if (key == 17) { g_igemm_ablate = value; return MTE_OK; }
-    if (key == 19) { g_igemm_pair_ksteps = value; return MTE_OK; }
-    if (key == 21) { g_igemm_pp = value; return MTE_OK; }
-    if (key == 23) { g_igemm8 = value; return MTE_OK; }
-    if (key == 24) { g_igemm8_min_tiles = value; return MTE_OK; }
-    if (key == 29) { g_igemm8_split_bn128 = value; return MTE_OK; }
-    if (key == 32) { g_igemm_n32_dma = value; return MTE_OK; }
     if (key == 14) return mtei_set_gn(3, value);
     if (key == 25) return mtei_set_gn(4, value);
     if (key == 4) { g_wgrad_dma = value; return MTE_OK; }
-    if (key == 6) { g_igemm_big = value; return MTE_OK; }
     if (key == 8) { g_wgrad_big = value; return MTE_OK; }
     if (key == 9) { g_wgrad_wgs = value; return MTE_OK; }
     if (key == 11) return mtei_set_patch_tall(value);
-    if (key == 7) { g_igemm_big_min_tiles = value; return MTE_OK; }
     return MTE_ERR_ARG;
 }
 #endif
@@ -1780,9 +1664,8 @@ int mte_conv2d_igemm(const void* x, long ldx, const void* wpack, const float* bi
     if (Cin_p % 8 != 0 || ldx % per16 != 0 || (KH & 1) == 0 || (KW & 1) == 0) return MTE_ERR_ARG;
     ConvArgs a{x, ldx, wpack, bias, y, ldy, out_f32, B, H, W, Cin_p, N, KH, KW, (long)B * H * W, 1, workspace, accumulate & 1, (accumulate >> 1) & 1,
                nullptr, nullptr};
-    if (dtype == MTE_DT_BF16) return dispatch_igemm<bf16_t>(a, workspace_elems, stream);
-    if (dtype == MTE_DT_F32) return dispatch_igemm<float>(a, workspace_elems, stream);
-    return MTE_ERR_UNSUPPORTED;
+    if (dtype != MTE_DT_BF16 && dtype != MTE_DT_F32) return MTE_ERR_UNSUPPORTED;
+    return plan_and_launch(a, dtype == MTE_DT_BF16 ? 2 : 4, workspace_elems, stream);
 }
 
 // The data gradient of a folded pack layer written WITHOUT the pixel-shuffle pass behind it (round 6): N = 4 C packed depths d = 4 c + s per pixel of the [B][H][W]
@@ -1795,8 +1678,7 @@ int mte_conv2d_igemm_unshuffle(const void* x, long ldx, const void* wpack, void*
     if (dtype != MTE_DT_BF16) return MTE_ERR_UNSUPPORTED;
     if (Cin_p % 8 != 0 || ldx % 8 != 0 || ldy % 8 != 0 || (KH & 1) == 0 || (KW & 1) == 0 || N % 32 != 0) return MTE_ERR_ARG;
     ConvArgs a{x, ldx, wpack, nullptr, y, ldy, 0, B, H, W, Cin_p, N, KH, KW, (long)B * H * W, 1, nullptr, accumulate & 1, 0, nullptr, nullptr, 0, N / 4};
-    if (!(g_igemm_dma == 1 && Cin_p % 32 == 0)) return MTE_ERR_UNSUPPORTED;
-    return dispatch_igemm<bf16_t>(a, 0, stream);
+    return plan_and_launch(a, 2, 0, stream);
 }
 
 // The same convolution over the ACTIVE SITES of a sparse map only (SAN branch): x / y are the dense zero-filled NHWC maps, `sites` the
@@ -1811,9 +1693,8 @@ int mte_conv2d_igemm_sparse(const void* x, long ldx, const void* wpack, const fl
     if (Cin_p % 8 != 0 || ldx % per16 != 0 || (KH & 1) == 0 || (KW & 1) == 0) return MTE_ERR_ARG;
     ConvArgs a{x, ldx, wpack, bias, y, ldy, 0, B, H, W, Cin_p, N, KH, KW, (long)B * H * W, 1, nullptr, accumulate & 1, (accumulate >> 1) & 1,
                sites, count};
-    if (dtype == MTE_DT_BF16) return dispatch_igemm<bf16_t>(a, 0, stream);
-    if (dtype == MTE_DT_F32) return dispatch_igemm<float>(a, 0, stream);
-    return MTE_ERR_UNSUPPORTED;
+    if (dtype != MTE_DT_BF16 && dtype != MTE_DT_F32) return MTE_ERR_UNSUPPORTED;
+    return plan_and_launch(a, dtype == MTE_DT_BF16 ? 2 : 4, 0, stream);
 }
 
 // dw_stage[N][KH*KW][Cin_p] (fp32) = sum over pixels of dy (x) shifted x.

@@ -445,43 +445,25 @@ __global__ __launch_bounds__(512, 2) void conv_igemm8_kernel(ConvArgs a) {
 }
 
 
-template <int BN, bool SM, bool ONE = false> int launch8(const ConvArgs& a, hipStream_t st) {
-    constexpr int LDS = 2 * (4 * 128 * 64 + 4 * (BN / 2) * 64);
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_igemm8_kernel<BN, SM, ONE>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return MTE_ERR_LAUNCH;
-        attr = true;
-    }
-    const long tiles = ((a.M + 255) / 256) * ((a.N + BN - 1) / BN);
-    hipLaunchKernelGGL((conv_igemm8_kernel<BN, SM, ONE>), dim3((unsigned)(tiles * a.splits)), dim3(512), LDS, st, a);
+template <auto Kernel> int launch8(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    if (mte_allow_lds<Kernel>(p.lds_bytes) != MTE_OK) return MTE_ERR_LAUNCH;
+    hipLaunchKernelGGL(Kernel, dim3(p.grid), dim3(p.threads), p.lds_bytes, st, a);
     return MTE_OK;
 }
 
 }  // namespace
 
-int g_igemm8_one = 1;                                // development knob (mte_debug_set(28, v)): 0 = the two-state loop everywhere
-// a.splits is final (1, or the number of fp32 slabs the caller's finish kernel adds); a.kslice selects the K order (ConvArgs); the caller checks the launch.
-int igemm8_launch(ConvArgs a, int bn, hipStream_t st) {
-    if (a.out_f32 || a.rows || a.Cin_p % 32 != 0 || a.N % 8 != 0 || (a.splits > 1 && (!a.ws || a.N % 4 != 0))) return MTE_ERR_UNSUPPORTED;
-    if (a.kslice && a.Cin_p % 64 != 0) return MTE_ERR_ARG;
-    if (((a.M - 1) * a.ldx + a.Cin_p) * 2 >= 0x7ff00000L || (long)a.N * a.KH * a.KW * a.Cin_p * 2 >= 0x7ff00000L || a.M >= 0x7fffff00L) return MTE_ERR_UNSUPPORTED;
+// the instances, chosen by plan_igemm (conv_plan.hpp): slice-major (SM; measured slower: development library only -- tests, tools/igemm8_locality.py), else one tap
+// state per K-tile (ONE) or two
+int igemm8_launch(const IgemmPlan& p, const ConvArgs& a, hipStream_t st) {
+    const bool wide = p.form == IgemmForm::P8_256x256;
+    if (p.kslice) {
 #ifdef MTE_DEV
-    if (a.kslice) {                                                  // (measured slower: development library only -- tests, tools/igemm8_locality.py)
-        if (bn == 256) return launch8<256, true>(a, st);
-        if (bn == 128) return launch8<128, true>(a, st);
-        return MTE_ERR_UNSUPPORTED;
-    }
+        return wide ? launch8<conv_igemm8_kernel<256, true>>(p, a, st) : launch8<conv_igemm8_kernel<128, true>>(p, a, st);
 #else
-    if (a.kslice) return MTE_ERR_UNSUPPORTED;
+        return MTE_ERR_UNSUPPORTED;
 #endif
-    // one tap state for both K-halves where they can never straddle a tap: 64-channel granularity and a split range that starts on an even K-step
-    const int ksteps = a.KH * a.KW * (a.Cin_p / 32);
-    const bool one = g_igemm8_one && a.Cin_p % 64 == 0 && (a.splits == 1 || ((ksteps + a.splits - 1) / a.splits) % 2 == 0);
-    if (one) {
-        if (bn == 256) return launch8<256, false, true>(a, st);
-        if (bn == 128) return launch8<128, false, true>(a, st);
     }
-    if (bn == 256) return launch8<256, false>(a, st);
-    if (bn == 128) return launch8<128, false>(a, st);
-    return MTE_ERR_UNSUPPORTED;
+    if (p.one) return wide ? launch8<conv_igemm8_kernel<256, false, true>>(p, a, st) : launch8<conv_igemm8_kernel<128, false, true>>(p, a, st);
+    return wide ? launch8<conv_igemm8_kernel<256, false>>(p, a, st) : launch8<conv_igemm8_kernel<128, false>>(p, a, st);
 }

@@ -1180,12 +1180,7 @@ template <int K, int NT, int SL, int NW = 4, int NH = 1, int THW = 8> int launch
     if (groups > ntiles) groups = ntiles;
     if (groups > parts_cap) groups = parts_cap < 1 ? 1 : parts_cap;   // one slab per workgroup group, always (round 4: no fp32-atomic combine on this launch path)
     a.groups = (int)groups;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv_patch_wgrad_kernel<K, NT, SL, NW, NH, THW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return MTE_ERR_LAUNCH;
-        attr_set = true;
-    }
+    if (mte_allow_lds<conv_patch_wgrad_kernel<K, NT, SL, NW, NH, THW>>((int)lds) != MTE_OK) return MTE_ERR_LAUNCH;
     if (a.groups > 1 && a.groups <= parts_cap) {                // one partial gradient per group, summed by the unpack pass
         a.part_stride = (long)a.N * K * K * a.Cin_p;
         if (parts_out) *parts_out = a.groups;

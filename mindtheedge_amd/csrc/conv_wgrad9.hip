@@ -346,12 +346,7 @@ __attribute__((visibility("hidden"))) int wgrad9_launch(const void* x, long ldx,
     a.part_stride = (long)N * 9 * Cin_p;
     if (parts_out) *parts_out = (int)splits;
     constexpr int LDS = 4 * (8 + 16) * 1024;
-    static bool attr = false;
-    if (!attr) {
-        if (hipFuncSetAttribute((const void*)conv_wgrad9_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)conv_wgrad9_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS) != hipSuccess) return MTE_ERR_LAUNCH;
-        attr = true;
-    }
+    if (mte_allow_lds<conv_wgrad9_kernel<1>>(LDS) != MTE_OK || mte_allow_lds<conv_wgrad9_kernel<2>>(LDS) != MTE_OK) return MTE_ERR_LAUNCH;
     const dim3 grid((unsigned)(a.base * splits));
     if (rk == 1) hipLaunchKernelGGL(conv_wgrad9_kernel<1>, grid, dim3(512), LDS, st, a);
     else hipLaunchKernelGGL(conv_wgrad9_kernel<2>, grid, dim3(512), LDS, st, a);

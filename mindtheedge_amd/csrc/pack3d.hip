@@ -1825,16 +1825,10 @@ inline P3LArgs upl_args(int B, int H, int W, int C, bool half_tile = false) {
     return a;
 }
 
-template <typename KF> int launch_p3l(KF kf, P3LArgs a, int grid, hipStream_t st, size_t lds_override = 0, int threads = 256) {
+template <auto KF> int launch_p3l(P3LArgs a, int grid, hipStream_t st, size_t lds_override = 0, int threads = 256) {
     const size_t lds = lds_override ? lds_override : p3_lds_bytes(a.C);
-    static const void* done[32] = {};
-    bool seen = false;
-    for (int i = 0; i < 32; ++i) seen = seen || done[i] == (const void*)kf;
-    if (!seen) {
-        if (hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, 112 * 1024) != hipSuccess) return MTE_ERR_LAUNCH;
-        for (int i = 0; i < 32; ++i) if (!done[i]) { done[i] = (const void*)kf; break; }
-    }
-    hipLaunchKernelGGL(kf, dim3(grid), dim3(threads), lds, st, a);
+    if (mte_allow_lds<KF>(112 * 1024) != MTE_OK) return MTE_ERR_LAUNCH;
+    hipLaunchKernelGGL(KF, dim3(grid), dim3(threads), lds, st, a);
     return mte_check_launch();
 }
 
@@ -1870,11 +1864,11 @@ int mte_pack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, vo
         l.tiles_h = (H / 2 + l.TH - 1) / l.TH; l.tiles_w = (W / 2 + l.TW - 1) / l.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
         l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
         const long grid = (long)l.ntiles * (4 * C / 128);
-        if (grid < (1L << 30)) return launch_p3l(pack3d_fwd_tr_kernel<2, 4>, l, (int)grid, stream, (size_t)4 * 18 * 448 + (size_t)8 * 1024);
+        if (grid < (1L << 30)) return launch_p3l<pack3d_fwd_tr_kernel<2, 4>>(l, (int)grid, stream, (size_t)4 * 18 * 448 + (size_t)8 * 1024);
     }
     if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
         P3LArgs l = p3l_args(B, H, W, C); l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
-        return launch_p3l(pack3d_fwd_lds_kernel, l, l.ntiles, stream);
+        return launch_p3l<pack3d_fwd_lds_kernel>(l, l.ntiles, stream);
     }
     if (C <= 256) { a.total *= 2; return launch_p3(dtype, pack3d_fwd_kernel<bf16_t, 4>, pack3d_fwd_kernel<float, 4>, a, a.total, stream); }
     return launch_p3(dtype, pack3d_fwd_kernel<bf16_t, 8>, pack3d_fwd_kernel<float, 8>, a, a.total, stream);
@@ -1891,12 +1885,12 @@ int mte_pack3d_bwd_data(const void* dout, long ldo, const float* w3, void* dx, l
         l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
         const long grid = (long)l.ntiles * (4 * C / 128);
         if (grid < (1L << 30))
-            return (g_p3_mfma_data & 16) ? launch_p3l(pack3d_bwd_data_mfma_kernel<false>, l, (int)grid, stream, (size_t)7 * 20 * 256)
-                                         : launch_p3l(pack3d_bwd_data_mfma_kernel<true>, l, (int)grid, stream, (size_t)7 * 20 * 256);
+            return (g_p3_mfma_data & 16) ? launch_p3l<pack3d_bwd_data_mfma_kernel<false>>(l, (int)grid, stream, (size_t)7 * 20 * 256)
+                                         : launch_p3l<pack3d_bwd_data_mfma_kernel<true>>(l, (int)grid, stream, (size_t)7 * 20 * 256);
     }
     if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
         P3LArgs l = p3l_args(B, H, W, C); l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l(pack3d_bwd_data_lds_kernel, l, l.ntiles, stream);
+        return launch_p3l<pack3d_bwd_data_lds_kernel>(l, l.ntiles, stream);
     }
     if (C <= 256) { a.total *= 2; return launch_p3(dtype, pack3d_bwd_data_kernel<bf16_t, 4>, pack3d_bwd_data_kernel<float, 4>, a, a.total, stream); }
     return launch_p3(dtype, pack3d_bwd_data_kernel<bf16_t, 8>, pack3d_bwd_data_kernel<float, 8>, a, a.total, stream);
@@ -1912,8 +1906,8 @@ int mte_pack3d_bwd_weight(const void* x, long ldx, const void* dout, long ldo, f
     if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
         P3LArgs l = p3l_args(B, H, W, C); l.x = (const bf16_t*)x; l.ldx = ldx; l.o = (const bf16_t*)dout; l.ldo = ldo; l.dwb = dwb;
         { const int dpairs = 4 * C / 16; l.dshift = (dpairs & (dpairs - 1)) == 0 ? __builtin_ctz(dpairs) : -1; l.tshift = __builtin_ctz(l.TW); }
-        if (g_p3_mfma) return launch_p3l(conv3d_bwd_weight_mfma_kernel<false>, l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, p3_lds_bytes(C) + 16, g_p3_mfma_threads);
-        return launch_p3l(pack3d_bwd_weight_lds_kernel, l, l.ntiles < 512 ? l.ntiles : 512, stream);
+        if (g_p3_mfma) return launch_p3l<conv3d_bwd_weight_mfma_kernel<false>>(l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, p3_lds_bytes(C) + 16, g_p3_mfma_threads);
+        return launch_p3l<pack3d_bwd_weight_lds_kernel>(l, l.ntiles < 512 ? l.ntiles : 512, stream);
     }
     if (C <= 256) a.total *= 2;
     long threads = a.total < 256L * 1024 ? a.total : 256L * 1024;
@@ -1936,21 +1930,21 @@ int mte_unpack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, 
         const int nh = g_p3_tr_passes;
         const size_t lds = (size_t)(l.TH + 2) * 18 * rs + (size_t)l.TH * 16 * 8 * C / nh;
         if (nh == 1) {
-            if (C == 32) return launch_p3l(unpack3d_fwd_tr_kernel<32, 8, 1>, l, l.ntiles, stream, lds);
-            if (C == 64) return launch_p3l(unpack3d_fwd_tr_kernel<64, 4, 1>, l, l.ntiles, stream, lds);
-            if (C == 128) return launch_p3l(unpack3d_fwd_tr_kernel<128, 2, 1>, l, l.ntiles, stream, lds);
-            return launch_p3l(unpack3d_fwd_tr_kernel<256, 1, 1>, l, l.ntiles, stream, lds);
+            if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 1>>(l, l.ntiles, stream, lds);
+            if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 1>>(l, l.ntiles, stream, lds);
+            if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 1>>(l, l.ntiles, stream, lds);
+            return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 1>>(l, l.ntiles, stream, lds);
         }
         if (nh == 2) {
-            if (C == 32) return launch_p3l(unpack3d_fwd_tr_kernel<32, 8, 2>, l, l.ntiles, stream, lds);
-            if (C == 64) return launch_p3l(unpack3d_fwd_tr_kernel<64, 4, 2>, l, l.ntiles, stream, lds);
-            if (C == 128) return launch_p3l(unpack3d_fwd_tr_kernel<128, 2, 2>, l, l.ntiles, stream, lds);
-            return launch_p3l(unpack3d_fwd_tr_kernel<256, 1, 2>, l, l.ntiles, stream, lds);
+            if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 2>>(l, l.ntiles, stream, lds);
+            if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 2>>(l, l.ntiles, stream, lds);
+            if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 2>>(l, l.ntiles, stream, lds);
+            return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 2>>(l, l.ntiles, stream, lds);
         }
-        if (C == 32) return launch_p3l(unpack3d_fwd_tr_kernel<32, 8, 4>, l, l.ntiles, stream, lds);
-        if (C == 64) return launch_p3l(unpack3d_fwd_tr_kernel<64, 4, 4>, l, l.ntiles, stream, lds);
-        if (C == 128) return launch_p3l(unpack3d_fwd_tr_kernel<128, 2, 4>, l, l.ntiles, stream, lds);
-        return launch_p3l(unpack3d_fwd_tr_kernel<256, 1, 4>, l, l.ntiles, stream, lds);
+        if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 4>>(l, l.ntiles, stream, lds);
+        if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 4>>(l, l.ntiles, stream, lds);
+        if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 4>>(l, l.ntiles, stream, lds);
+        return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 4>>(l, l.ntiles, stream, lds);
     }
     if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 8) && (C == 32 || C == 64) && ((long)B * H * W - 1) * ldx + C < (1L << 30)) {
         P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
@@ -1960,11 +1954,11 @@ int mte_unpack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, 
         const size_t lds = (size_t)2 * (((l.TH + 2) * 18 + 15) / 16) * (C / 8 + 2) * 256;      // two tile buffers
         const int grid = l.ntiles < g_p3_persist_wgs ? l.ntiles : g_p3_persist_wgs;            // persistent workgroups (a multiple of 8: tile % 8 = XCD)
         if (g_p3_mfma_data & 16) {
-            if (C == 32) return launch_p3l(unpack3d_fwd_mfma_kernel<32, false>, l, grid, stream, lds);
-            return launch_p3l(unpack3d_fwd_mfma_kernel<64, false>, l, grid, stream, lds);
+            if (C == 32) return launch_p3l<unpack3d_fwd_mfma_kernel<32, false>>(l, grid, stream, lds);
+            return launch_p3l<unpack3d_fwd_mfma_kernel<64, false>>(l, grid, stream, lds);
         }
-        if (C == 32) return launch_p3l(unpack3d_fwd_mfma_kernel<32, true>, l, grid, stream, lds);
-        return launch_p3l(unpack3d_fwd_mfma_kernel<64, true>, l, grid, stream, lds);
+        if (C == 32) return launch_p3l<unpack3d_fwd_mfma_kernel<32, true>>(l, grid, stream, lds);
+        return launch_p3l<unpack3d_fwd_mfma_kernel<64, true>>(l, grid, stream, lds);
     }
     a.total = (long)B * H * W * (C / 8);
     return launch_p3(dtype, unpack3d_fwd_kernel<bf16_t>, unpack3d_fwd_kernel<float>, a, a.total, stream);
@@ -1981,27 +1975,27 @@ int mte_unpack3d_bwd_data(const void* dout, long ldo, const float* w3, void* dx,
         l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
         const size_t lds = (size_t)4 * (l.TH + 2) * (l.TW + 2) * (C + 16) * 2;
         if (C == 32 && (g_p3_mfma_data & 2) && ((long)B * 4 * H * W - 1) * ldo + 32 < (1L << 30)) {
-            if (g_p3_mfma_data & 16) return launch_p3l(unpack3d_bwd_data_dma32_kernel<4, false>, l, l.ntiles, stream, (size_t)180 * 256, 256);
-            if (g_p3_mfma_data & 4) return launch_p3l(unpack3d_bwd_data_dma32_kernel<4, true>, l, l.ntiles, stream, (size_t)180 * 256, 256);
-            return launch_p3l(unpack3d_bwd_data_dma32_kernel<2, true>, l, l.ntiles, stream, (size_t)180 * 256, 128);
+            if (g_p3_mfma_data & 16) return launch_p3l<unpack3d_bwd_data_dma32_kernel<4, false>>(l, l.ntiles, stream, (size_t)180 * 256, 256);
+            if (g_p3_mfma_data & 4) return launch_p3l<unpack3d_bwd_data_dma32_kernel<4, true>>(l, l.ntiles, stream, (size_t)180 * 256, 256);
+            return launch_p3l<unpack3d_bwd_data_dma32_kernel<2, true>>(l, l.ntiles, stream, (size_t)180 * 256, 128);
         }
         if (g_p3_mfma_data & 16) {
-            if (C == 32) return launch_p3l(unpack3d_bwd_data_mfma_kernel<32, false>, l, l.ntiles, stream, lds);
-            return launch_p3l(unpack3d_bwd_data_mfma_kernel<64, false>, l, l.ntiles, stream, lds);
+            if (C == 32) return launch_p3l<unpack3d_bwd_data_mfma_kernel<32, false>>(l, l.ntiles, stream, lds);
+            return launch_p3l<unpack3d_bwd_data_mfma_kernel<64, false>>(l, l.ntiles, stream, lds);
         }
-        if (C == 32) return launch_p3l(unpack3d_bwd_data_mfma_kernel<32, true>, l, l.ntiles, stream, lds);
-        return launch_p3l(unpack3d_bwd_data_mfma_kernel<64, true>, l, l.ntiles, stream, lds);
+        if (C == 32) return launch_p3l<unpack3d_bwd_data_mfma_kernel<32, true>>(l, l.ntiles, stream, lds);
+        return launch_p3l<unpack3d_bwd_data_mfma_kernel<64, true>>(l, l.ntiles, stream, lds);
     }
     if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && C % 32 == 0 && C <= 128) {
         P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
         const P3Tile t = up4_tile(C); l.TH = t.TH; l.TW = t.TW;
         l.tiles_h = (H + t.TH - 1) / t.TH; l.tiles_w = (W + t.TW - 1) / t.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
         l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l(unpack3d_bwd_data_lds4_kernel, l, l.ntiles, stream, up4_lds_bytes(C));
+        return launch_p3l<unpack3d_bwd_data_lds4_kernel>(l, l.ntiles, stream, up4_lds_bytes(C));
     }
     if (dtype == MTE_DT_BF16 && g_p3_lds && C % 32 == 0 && C <= 512) {
         P3LArgs l = upl_args(B, H, W, C); l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l(unpack3d_bwd_data_lds_kernel, l, l.ntiles, stream, up_lds_bytes(C));
+        return launch_p3l<unpack3d_bwd_data_lds_kernel>(l, l.ntiles, stream, up_lds_bytes(C));
     }
     a.total = (long)B * H * W * (C / 8);
     return launch_p3(dtype, unpack3d_bwd_data_kernel<bf16_t>, unpack3d_bwd_data_kernel<float>, a, a.total, stream);
@@ -2017,8 +2011,8 @@ int mte_unpack3d_bwd_weight(const void* x, long ldx, const void* dout, long ldo,
         const size_t lds = (size_t)(l.TH + 2) * (l.TW + 2) * LDP(C) * 2;
         const int cap = g_p3_small_tiles ? 1024 : 512;
         { const int dpairs = C / 16; l.dshift = (dpairs & (dpairs - 1)) == 0 ? __builtin_ctz(dpairs) : -1; l.tshift = __builtin_ctz(l.TW); }
-        if (g_p3_mfma) return launch_p3l(conv3d_bwd_weight_mfma_kernel<true>, l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, lds + 16, g_p3_mfma_threads);
-        return launch_p3l(unpack3d_bwd_weight_lds_kernel, l, l.ntiles < cap ? l.ntiles : cap, stream, lds);
+        if (g_p3_mfma) return launch_p3l<conv3d_bwd_weight_mfma_kernel<true>>(l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, lds + 16, g_p3_mfma_threads);
+        return launch_p3l<unpack3d_bwd_weight_lds_kernel>(l, l.ntiles < cap ? l.ntiles : cap, stream, lds);
     }
     a.total = (long)B * H * W * (C / 8);
     long threads = a.total < 256L * 2048 ? a.total : 256L * 2048;

@@ -206,11 +206,7 @@ int tap_launch(TapWgradArgs a, int max_wgs, int* groups, hipStream_t st) {
     constexpr int C = 16 * CB;
     constexpr size_t ring = (size_t)4 * RING * (64 * C + 512), red = (size_t)4 * (C * 9 + 1) * sizeof(float);
     constexpr size_t lds = ring > red ? ring : red;
-    static int configured = 0;
-    if (!configured) {
-        if (hipFuncSetAttribute((const void*)tap_wgrad_mfma_kernel<CB, RING>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return MTE_ERR_LAUNCH;
-        configured = 1;
-    }
+    if (mte_allow_lds<tap_wgrad_mfma_kernel<CB, RING>>((int)lds) != MTE_OK) return MTE_ERR_LAUNCH;
     if (!g_tap_cus) {
         int dev = 0; hipDeviceProp_t p;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&p, dev) != hipSuccess) return MTE_ERR_LAUNCH;

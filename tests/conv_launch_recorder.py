@@ -1,0 +1,259 @@
+"""Launch recorder of the implicit-GEMM convolution: which kernel instance, grid, block and dynamic LDS every case gets, found on the CPU.
+
+conv_igemm.hip and conv_igemm8.hip are compiled for the host alone (hipcc --cuda-host-only) with tests/conv_launch_shim.hpp in front, which turns every launch
+into a line of text, and linked with tests/conv_launch_driver.cpp, which calls the three C entry points.  tests/conv_launch_table.json holds one line per case:
+the case (the driver's input line) and what was launched.  tests/test_conv_launch_table_cpu.py requires the working tree to reproduce every line.
+
+    python tests/conv_launch_recorder.py --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+"""
+import argparse
+import json
+import os
+import re
+import subprocess
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+TESTS = os.path.join(ROOT, "tests")
+CSRC = os.path.join(ROOT, "mindtheedge_amd", "csrc")
+TABLE = os.path.join(TESTS, "conv_launch_table.json")
+HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
+SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
+BF16, F32 = 0, 1
+SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
+
+
+def build(out_dir, dev, csrc=CSRC, extra=()):
+    """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs)"""
+    exe = os.path.join(out_dir, "recorder_dev" if dev else "recorder")
+    cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
+    cmd += ["-DMTE_DEV"] if dev else []
+    cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip"), os.path.join(TESTS, "conv_launch_driver.cpp"), "-o", exe]
+    subprocess.run(cmd, check=True, capture_output=True, text=True)
+    return exe
+
+
+def run(exe, case_lines):
+    """-> the driver's output lines, one per case"""
+    out = subprocess.run([exe], input="\n".join(case_lines) + "\n", capture_output=True, text=True)
+    if out.returncode != 0:
+        raise RuntimeError("recorder failed: " + out.stderr[-2000:])
+    lines = out.stdout.splitlines()
+    assert len(lines) == len(case_lines)
+    return lines
+
+
+def splitk_workspace_elems(M, N):
+    """what kernels._splitk_workspace offers for an [M][N] output"""
+    return 0 if ((M + 127) // 128) * ((N + 127) // 128) >= 384 else SPLITK_SLABS * M * N
+
+
+def round8(c):
+    return (c + 7) // 8 * 8
+
+
+def case(entry, dtype, B, H, W, cin_p, N, k, ldx=None, out_f32=0, ws=None, accumulate=0, knobs=None):
+    """ws: None = no workspace, else the element count offered with a non-null pointer"""
+    ks = ",".join("%d=%d" % kv for kv in knobs) if knobs else "-"
+    return "%s %d %d %d %d %d %d %d %d %d %d %d %d %d %s" % (entry, dtype, B, H, W, cin_p, N, k, k, cin_p if ldx is None else ldx, out_f32,
+                                                             0 if ws is None else 1, ws or 0, accumulate, ks)
+
+
+def training_shapes():
+    """every mte_conv2d_igemm / mte_conv2d_igemm_unshuffle shape of the T8 training step (profiles/r06_v7_conv_table.txt)"""
+    seen = []
+    with open(os.path.join(ROOT, "profiles", "r06_v7_conv_table.txt")) as f:
+        for line in f:
+            m = re.search(r"(mte_conv2d_igemm(?:_unshuffle)?)\s+B,H,W,Cin_p,N,KH,KW=\((.*)\)", line)
+            if m:
+                key = (m.group(1),) + tuple(int(v) for v in m.group(2).split(","))
+                if key not in seen:
+                    seen.append(key)
+    return seen
+
+
+# ---- the shapes and knob settings of tests/test_gpu_conv_variants.py and tools/igemm_ablate.py, igemm8_check.py, igemm_race_stress.py (cin, cout, k, B, H, W[, ldx])
+T_256 = [(64, 128, 3, 2, 24, 40), (96, 256, 3, 3, 10, 52), (32, 128, 5, 1, 30, 33), (128, 384, 1, 2, 16, 48)]
+T_PP = [(256, 256, 3, 8, 48, 160), (64, 256, 5, 2, 96, 320), (96, 512, 3, 3, 10, 52), (128, 256, 1, 8, 48, 160), (32, 256, 1, 2, 16, 48), (64, 512, 1, 1, 24, 40),
+        (96, 256, 1, 2, 10, 52)]
+T_SPLIT = [(512, 256, 3, 4, 32, 40), (1024, 512, 3, 2, 40, 64)]
+T_192 = [(32, 72, 3, 2, 24, 40), (64, 88, 3, 1, 30, 33), (96, 96, 1, 2, 16, 48), (32, 72, 3, 1, 17, 31)]
+T_IGEMM8 = [(64, 256, 3, 2, 24, 40, None), (96, 256, 3, 3, 10, 52, None), (32, 384, 5, 1, 17, 33, None), (128, 384, 1, 2, 16, 48, None),
+            (256, 256, 3, 2, 48, 80, None), (64, 200, 3, 2, 40, 64, 96), (128, 128, 3, 2, 48, 96, None), (96, 128, 3, 1, 33, 47, None),
+            (512, 104, 3, 1, 24, 80, None), (160, 136, 3, 1, 31, 45, 200), (32, 128, 7, 1, 64, 96, None), (1024, 512, 3, 1, 12, 40, None)]
+TOOL_ABLATE = [(512, 512, 3, 8, 24, 80), (256, 256, 3, 8, 48, 160), (128, 128, 3, 8, 96, 320), (512, 128, 5, 8, 48, 160)]
+TOOL_CHECK = T_IGEMM8 + [(32, 256, 3, 1, 30, 33, None), (256, 256, 3, 8, 48, 160, None), (64, 256, 5, 4, 96, 320, None), (384, 256, 3, 2, 48, 160, None),
+                         (128, 512, 3, 8, 24, 80, None), (256, 256, 1, 8, 48, 160, None), (128, 128, 3, 2, 96, 320, None), (2048, 256, 3, 2, 12, 40, None)]
+TOOL_BENCH = [(32, 128, 7, 192, 640), (4096, 256, 3, 24, 80), (8192, 512, 3, 12, 40), (256, 4096, 3, 24, 80), (512, 8192, 3, 12, 40), (512, 128, 5, 48, 160),
+              (64, 256, 5, 96, 320), (128, 512, 5, 48, 160), (64, 104, 3, 192, 640), (512, 768, 3, 24, 80), (128, 200, 3, 96, 320), (768, 512, 3, 24, 80),
+              (256, 384, 3, 48, 160), (128, 128, 3, 96, 320), (512, 512, 3, 24, 80), (384, 256, 3, 48, 160), (256, 256, 3, 48, 160), (512, 256, 3, 24, 80),
+              (64, 128, 3, 96, 320), (256, 128, 3, 48, 160), (128, 256, 3, 48, 160), (256, 512, 3, 24, 80), (512, 512, 3, 12, 40), (128, 128, 1, 96, 320),
+              (256, 256, 1, 48, 160), (512, 512, 1, 24, 80), (192, 128, 3, 96, 320), (128, 192, 3, 96, 320)]
+TOOL_RACE = T_256 + [(256, 256, 3, 8, 48, 160), (64, 256, 5, 4, 96, 320), (384, 256, 3, 2, 48, 160), (128, 512, 3, 8, 24, 80), (256, 256, 1, 8, 48, 160)]
+
+
+def cases():
+    out = []
+
+    def add(*a, **kw):
+        c = case(*a, **kw)
+        if c not in out:
+            out.append(c)
+
+    # ---- the training step: with the workspace kernels._splitk_workspace passes and with none, solo or not, bf16 and fp32
+    for entry, B, H, W, cin_p, N, kh, kw in training_shapes():
+        M = B * H * W
+        if entry == "mte_conv2d_igemm_unshuffle":
+            for dtype in (BF16, F32):
+                for acc in (0, 1):
+                    add("unshuffle", dtype, B, H, W, cin_p, N, kh, accumulate=acc)
+            continue
+        for dtype in (BF16, F32):
+            for ws in (splitk_workspace_elems(M, N) or None, None):
+                for acc in (0, SOLO):
+                    add("igemm", dtype, B, H, W, cin_p, N, kh, ws=ws, accumulate=acc)
+
+    for entry in ("igemm", "sparse", "unshuffle"):                      # an element type the library does not have
+        add(entry, 2, 8, 48, 160, 256, 256, 3)
+
+    # ---- tests/test_gpu_conv_variants.py (K.conv_forward: solo launches; with and without accumulation the choice is the same, one of the two is recorded)
+    for cin, cout, k, B, H, W in T_256:
+        for big in (0, 1, 2):
+            kn = [(6, big), (23, 0), (7, 1)]
+            add("igemm", BF16, B, H, W, round8(cin), cout, k, accumulate=SOLO, knobs=kn)
+            if round8(cin) % 128 == 0:
+                add("igemm", BF16, B, H, W, cout, round8(cin), k, accumulate=SOLO, knobs=kn)
+    for cin, cout, k, B, H, W in T_PP:
+        for big, pp in ((0, 0), (2, 1), (2, 0)):
+            add("igemm", BF16, B, H, W, round8(cin), cout, k, accumulate=SOLO, knobs=[(6, big), (23, 0), (7, 1), (21, pp)])
+    for cin, cout, k, B, H, W in T_SPLIT:
+        for big in (2, 0):
+            add("igemm", BF16, B, H, W, cin, cout, k, ws=splitk_workspace_elems(B * H * W, cout) or None, accumulate=SOLO, knobs=[(6, big), (23, 0)])
+    for cin, cout, k, B, H, W in T_192:
+        for big in (0, 3):
+            add("igemm", BF16, B, H, W, round8(cin), cout, k, accumulate=SOLO, knobs=[(6, big), (23, 0), (7, 1)])
+    for cin, cout, k, B, H, W, ldx in T_IGEMM8:
+        M = B * H * W
+        for v8 in (0, 39, 7):
+            for split in (False, True):
+                add("igemm", BF16, B, H, W, round8(cin), cout, k, ldx=ldx, ws=8 * M * cout if split else None, accumulate=SOLO,
+                    knobs=[(23, v8), (24, 1000000 if split else 1), (6, 0)])
+        if round8(cin) % 64 == 0:
+            for one in (1, 0):
+                for split in (False, True):
+                    add("igemm", BF16, B, H, W, round8(cin), cout, k, ldx=ldx, ws=8 * M * cout if split else None, accumulate=SOLO,
+                        knobs=[(23, 39), (6, 0), (28, one), (24, 1000000 if split else 1)])
+
+    # ---- tools/igemm_ablate.py, igemm8_check.py, igemm_race_stress.py
+    for big in (2, 1, 0):
+        for cin, cout, k, B, H, W in TOOL_ABLATE:
+            for abl in (0, 1, 2, 4, 3, 5, 6, 7):
+                add("igemm", BF16, B, H, W, cin, cout, k, accumulate=SOLO, knobs=[(15, 4), (6, big), (7, 100 if big == 2 else 224), (17, abl)])
+    for cin, cout, k, B, H, W, ldx in TOOL_CHECK:
+        M = B * H * W
+        for split in (False, True):
+            for v8 in (0, 39, 7):
+                add("igemm", BF16, B, H, W, round8(cin), cout, k, ldx=ldx, ws=8 * M * cout if split else None, accumulate=SOLO,
+                    knobs=[(23, v8), (24, 1000000 if split else 1), (6, 0)])
+    for cin, cout, k, H, W in TOOL_BENCH:
+        for v8 in (0, 3, 7, 35):
+            add("igemm", BF16, 8, H, W, cin, cout, k, ws=splitk_workspace_elems(8 * H * W, cout) or None, accumulate=SOLO, knobs=[(23, v8)])
+    for cin, cout, k, B, H, W in TOOL_RACE:
+        for big, pp, v8 in ((0, 0, 0), (1, 0, 0), (2, 0, 0), (2, 1, 0), (0, 0, 39), (0, 0, 7)):
+            add("igemm", BF16, B, H, W, round8(cin), cout, k, accumulate=SOLO, knobs=[(6, big), (7, 1), (21, pp), (23, v8), (24, 1)])
+
+    # ---- boundaries, one group at a time around three base shapes (B, H, W, Cin_p, N, k); fp32 beside bf16 on the first
+    bases = [(8, 48, 160, 256, 256, 3), (8, 24, 80, 512, 512, 3), (8, 96, 320, 128, 128, 3)]
+    for i, (B, H, W, cin_p, N0, k) in enumerate(bases):
+        M = B * H * W
+        for dtype in (BF16, F32) if i == 0 else (BF16,):
+            wss = (None, 8 * M) if dtype == BF16 else (None,)              # (slabs per output element)
+            for n in (32, 33, 64, 65, 68, 96, 97, 128, 129, 200, 256, 328, 384, 456):
+                for ws in wss:
+                    add("igemm", dtype, B, H, W, cin_p, n, k, ws=ws and ws * n)
+            for c in (8, 24, 32, 40, 64, 72, 512, 8192):
+                for ws in wss:
+                    add("igemm", dtype, B, H, W, c, N0, k, ws=ws and ws * N0)
+            for kk in (1, 3, 5, 7):
+                for ws in wss:
+                    add("igemm", dtype, B, H, W, cin_p, N0, kk, ws=ws and ws * N0)
+            for ws in (0, M * N0, 2 * M * N0, 8 * M * N0):
+                for acc in (0, SOLO):
+                    add("igemm", dtype, B, H, W, cin_p, N0, k, ws=ws, accumulate=acc)
+            for n in (32, 96, 128, 256):
+                add("igemm", dtype, B, H, W, cin_p, n, k, out_f32=1, ws=8 * M * n)
+                add("sparse", dtype, B, H, W, cin_p, n, k, accumulate=SOLO)
+            for n in (32, 128, 256, 512, 100):
+                for c in (cin_p, 40):
+                    add("unshuffle", dtype, B, H, W, c, n, k)
+    # every knob away from its default, on the first base shape (and where it steers the split-K rule, on two few-tile shapes)
+    knob_sets = [[(23, 0)], [(23, 0), (6, 0)], [(23, 0), (6, 1)], [(23, 0), (6, 2)], [(23, 0), (21, 0)], [(23, 19)], [(23, 23)], [(23, 55)], [(23, 50)], [(23, 49)],
+                 [(0, 0)], [(0, 2)], [(32, 0)], [(15, 1), (23, 0)], [(15, 3), (23, 0)], [(15, 4), (23, 0)], [(19, 0), (23, 0)], [(19, 1000), (23, 0)], [(29, 0)],
+                 [(29, 1000)], [(28, 0)], [(24, 1)], [(24, 1000000)], [(7, 1)], [(7, 1000000)], [(7, 1), (23, 0)], [(7, 1000000), (23, 0)]]
+    B, H, W, cin_p, N0, k = bases[0]
+    M = B * H * W
+    for kn in knob_sets:
+        for n in (32, 128, 256):
+            for ws in (None, 8 * M * n):
+                add("igemm", BF16, B, H, W, cin_p, n, k, ws=ws, accumulate=SOLO if kn[0][0] in (15, 19) and ws is None else 0, knobs=kn)
+        for b2, h2, w2 in ((8, 24, 80), (8, 12, 40)):
+            add("igemm", BF16, b2, h2, w2, 512, 512, 3, ws=8 * b2 * h2 * w2 * 512, knobs=kn)
+        if kn[0][0] in (0, 32):                                            # the loader knobs: every form that has another loader, and the forms that need one
+            for dtype, c, n in ((F32, cin_p, 32), (F32, cin_p, 64), (F32, cin_p, 128), (BF16, cin_p, 64), (BF16, 40, 64), (BF16, cin_p, 96)):
+                add("igemm", dtype, B, H, W, c, n, k, knobs=kn)
+            add("unshuffle", BF16, B, H, W, cin_p, 128, k, knobs=kn)
+            add("sparse", BF16, B, H, W, cin_p, N0, k, knobs=kn)
+    # tile counts on both sides of every threshold, for each tile height (one image row of M pixels; 384: where choose_splits stops splitting four-wave tiles)
+    for height, ns, ts in ((128, (128,), (96, 128, 200, 224, 256, 384, 512)), (192, (96,), (96, 128, 200, 224, 256, 512)), (256, (128, 256), (96, 128, 200, 224, 256, 512))):
+        for t in ts:
+            for M in (height * (t - 1), height * (t - 1) + 1):
+                for n in ns:
+                    for ws in (None, 8 * M * n):
+                        for kn in (None, [(23, 0)]):
+                            add("igemm", BF16, 1, 1, M, 256, n, 3, ws=ws, knobs=kn)
+                if height == 256:
+                    add("igemm", BF16, 1, 1, M, 64, 256, 1, ws=8 * M * 256)                  # (two K-steps: too short a reduction to split)
+                    add("igemm", BF16, 1, 1, M, 64, 128, 3, knobs=[(23, 0)])               # (18 K-steps: the two-workgroup ring of the 256 x 128 tile)
+    # one ldx on each side of the activation bound, one Cin_p on each side of the weight bound (both 0x7ff00000 bytes), for every form that asks
+    for dtype, es in ((BF16, 2), (F32, 4)):
+        for B, H, W, cin_p, n, k in ((8, 48, 160, 256, 256, 3), (8, 48, 160, 256, 32, 3), (8, 48, 160, 256, 96, 3)):
+            M = B * H * W
+            edge = ((0x7ff00000 - 1) // es - cin_p) // (M - 1)                          # largest ldx inside the bound
+            for ldx in (edge // 8 * 8, edge // 8 * 8 + 8):
+                for kn in (None, [(23, 0)]):
+                    add("igemm", dtype, B, H, W, cin_p, n, k, ldx=ldx, knobs=kn)
+                add("unshuffle", dtype, B, H, W, cin_p, n, k, ldx=ldx)
+        for n, k in ((512, 7), (32, 7)):
+            edge = (0x7ff00000 - 1) // es // (n * k * k)
+            for c in (edge // 64 * 64, edge // 64 * 64 + 64):
+                for kn in (None, [(23, 0)]):
+                    add("igemm", dtype, 1, 16, 32, c, n, k, knobs=kn)
+    return out
+
+
+def record(csrc=CSRC, dev=True, extra=()):
+    with tempfile.TemporaryDirectory() as tmp:
+        cs = cases()
+        return run(build(tmp, dev, csrc, extra), cs if dev else [c for c in cs if c.endswith(" -")])
+
+
+def load_table():
+    """-> the table's lines (the file is a JSON array with one case per line)"""
+    with open(TABLE) as f:
+        return [line.rstrip(",\n") for line in f if line.startswith("{")]
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--csrc", default=CSRC)
+    ap.add_argument("--out")
+    ap.add_argument("--write", action="store_true")
+    ap.add_argument("--product", action="store_true", help="the build without -DMTE_DEV: the cases that set no knob")
+    a = ap.parse_args()
+    lines = record(a.csrc, dev=not a.product)
+    for ln in lines:
+        json.loads(ln)
+    with open(TABLE if a.write else a.out, "w") as f:
+        f.write("[\n" + ",\n".join(lines) + "\n]\n")
+    print("%d cases" % len(lines))

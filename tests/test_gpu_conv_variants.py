@@ -155,8 +155,7 @@ def test_igemm_256x128_tiles_match_128x128_tiles(shape, devlib):
             return y.float().cpu(), None if dx is None else dx.float().cpu()
         finally:
             K._splitk_workspace = orig
-            K.lib.mte_debug_set(6, 3); K.lib.mte_debug_set(23, 51)
-            K.lib.mte_debug_set(7, 224)
+            K.lib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
 
     K.use_patch_kernels(False)
     try:
@@ -202,9 +201,7 @@ def test_igemm_pingpong_loop_matches_one_barrier_loop(shape, devlib):
     finally:
         K._splitk_workspace = orig
         K.use_patch_kernels(True)
-        K.lib.mte_debug_set(6, 3); K.lib.mte_debug_set(23, 51)
-        K.lib.mte_debug_set(7, 224)
-        K.lib.mte_debug_set(21, 1)
+        K.lib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
 
 
 @pytest.mark.parametrize("shape", [(512, 256, 3, 4, 32, 40), (1024, 512, 3, 2, 40, 64)])
@@ -229,7 +226,7 @@ def test_big_tile_split_k_matches_small_tiles(shape, devlib):
         assert torch.equal(outs[0], outs[2]) and torch.equal(outs[1], outs[3])
         assert float(outs[0].abs().mean()) > 0.1                 # (not trivially zero)
     finally:
-        K.lib.mte_debug_set(6, 3); K.lib.mte_debug_set(23, 51)
+        K.lib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
         K.use_patch_kernels(True)
 
 
@@ -257,8 +254,7 @@ def test_igemm_192x96_tiles_match_128x128_tiles(shape, devlib):
             return y.float().cpu(), acc.float().cpu()
         finally:
             K._splitk_workspace = orig
-            K.lib.mte_debug_set(6, 3); K.lib.mte_debug_set(23, 51)
-            K.lib.mte_debug_set(7, 224)
+            K.lib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
 
     K.use_patch_kernels(False)
     try:
@@ -337,14 +333,14 @@ def test_eight_phase_igemm_against_the_128x128_tile(devlib, shape, order):
         assert one_rounding(first, run(0, False, False))
     finally:
         K._splitk_workspace = saved
-        devlib.mte_debug_set(23, 51); devlib.mte_debug_set(24, 200); devlib.mte_debug_set(6, 3)
+        devlib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
         K.use_patch_kernels(True)
 
 
 @pytest.mark.parametrize("shape", [s_ for s_ in IGEMM8_SHAPES if ((s_[0] + 7) // 8 * 8) % 64 == 0])
 def test_eight_phase_one_tap_state_loop_matches_the_two_state_loop(devlib, shape):
     """round-5 advisor: the shipped default of conv_igemm8_kernel where Cin_p % 64 == 0 is the ONE form (both K-halves of a K-tile from one tap state,
-    g_igemm8_one = 1) -- it had no on / off test of its own.  Development knob 28 = 0 runs the general two-state loop on the same launch: the same K-steps in
+    IgemmKnobs.igemm8_one = 1) -- it had no on / off test of its own.  Development knob 28 = 0 runs the general two-state loop on the same launch: the same K-steps in
     the same order, so the outputs must be bit-identical -- unsplit, accumulating, and under split-K (where the ONE form also needs an even K-step count per
     split: the launcher's own rule decides, the test only flips the knob)."""
     from mindtheedge_amd import kernels as K
@@ -376,7 +372,7 @@ def test_eight_phase_one_tap_state_loop_matches_the_two_state_loop(devlib, shape
             assert torch.equal(run(1, split, accumulate), run(0, split, accumulate)), (shape, split, accumulate)
     finally:
         K._splitk_workspace = saved
-        devlib.mte_debug_set(28, 1); devlib.mte_debug_set(23, 51); devlib.mte_debug_set(24, 200); devlib.mte_debug_set(6, 3)
+        devlib.mte_debug_set(33, 0)                     # every implicit-GEMM knob back to its default (IgemmKnobs{}, csrc/conv_plan.hpp)
         K.use_patch_kernels(True)
 
 
