@@ -1628,7 +1628,7 @@ extern "C" {
 // development knobs (libmte_hip_dev.so only, -DMTE_DEV): the implicit-GEMM keys are IgemmKnobs (conv_plan.hpp); key 1 = conv3d pack stencils
 // (1 = LDS-tiled, 0 = gather).  Not part of the product contract.
 extern "C" int mtei_set_pack3d_lds(int value);
-extern "C" int mtei_set_gn(int which, int value);
+extern "C" int mtei_set_gn(int key, int value);
 extern "C" int mtei_set_patch_tall(int v);
 extern "C" int mtei_set_tap_wgrad(int v);            // tap_wgrad.hip
 extern "C" int mtei_set_head_mfma(int v);
@@ -1640,10 +1640,7 @@ int mte_debug_set(int key, int value) {
     if (key == 30) return mtei_set_head_mfma(value);
     if (key == 31) return mtei_set_tap_wgrad(value);
     if (key == 1) return mtei_set_pack3d_lds(value);
-    if (key == 2 || key == 3) return mtei_set_gn(key - 2, value);
-    if (key == 13) return mtei_set_gn(2, value);
-    if (key == 14) return mtei_set_gn(3, value);
-    if (key == 25) return mtei_set_gn(4, value);
+    if (key == 2 || key == 3 || key == 13 || key == 14 || key == 25) return mtei_set_gn(key, value);      // GnKnobs (gn_plan.hpp)
     if (key == 4) { g_wgrad_dma = value; return MTE_OK; }
     if (key == 8) { g_wgrad_big = value; return MTE_OK; }
     if (key == 9) { g_wgrad_wgs = value; return MTE_OK; }

@@ -915,135 +915,16 @@ __global__ __launch_bounds__(256, 4) void gn_bwd_cluster_kernel(GnArgs a) {
     }
 }
 
-int g_gn_min_rows = 32, g_gn_target = 2048;         // development knobs (mte_debug_set(2 / 3, v))
-int g_gn_slab = 1;                                  // development knob (mte_debug_set(13, v)): 0 = stream kernels only
+}  // namespace
 
-int g_gn_zigzag = 1;                                // development knob (mte_debug_set(14, v))
+#include <type_traits>
+#include "gn_plan.hpp"                              // the choice of kernels: plan_gn, GnKnobs
 
-// Two-pass kernels read the same tensors twice.  Blocks are dispatched in blockIdx order, i.e. sample after sample: when the
-// second pass walks the samples in the OPPOSITE order it starts on the bytes the first pass touched last, which are still in
-// the 256 MB Infinity Cache (a full-resolution 32-channel activation is 252 MB per tensor at T8: in the same order nothing
-// of the first pass survives to the second).
-int gn_blocks(int B, int HW, int rstep, bool forward = false) {
-    // ~8 workgroups per CU across the batch, at least min_rows pixels per thread row: a thread's rows are consumed in serial
-    // batches of GN_U loads, so long runs leave the short low-resolution launches latency-bound; the backward kernels pay a
-    // per-workgroup flush of 2-3 C atomics and prefer fewer, longer workgroups
-    const int min_rows = forward ? (g_gn_min_rows < 16 ? g_gn_min_rows : 16) : g_gn_min_rows;
-    long want = (g_gn_target + B - 1) / B;
-    long maxb = ((long)HW + (long)min_rows * rstep - 1) / ((long)min_rows * rstep);
-    if (want > maxb) want = maxb;
-    return (int)(want < 1 ? 1 : want);
-}
+namespace {
 
-bool gn_shape_ok(int C, int dtype) {
-    const int per16 = dtype == MTE_DT_BF16 ? 8 : 4;
-    if (C % GN_GROUPS != 0 || C % per16 != 0) return false;
-    const int cpr = C / per16;
-    return cpr <= 256 && 256 % cpr == 0;
-}
+static_assert(GN_PLAN_GROUPS == GN_GROUPS && GnKnobs{}.spin_max == GN_SPIN_MAX, "gn_plan.hpp repeats these two");
 
-// slab geometry: a group must be whole 16-byte chunks (1, 2, 4 or 8 per pixel); -> chunks of one slab, or 0 if not a slab shape
-long slab_chunks(int HW, int C, int dtype, int* cps_shift) {
-    const int per16 = dtype == MTE_DT_BF16 ? 8 : 4;
-    const int gs = C / GN_GROUPS;
-    if (!g_gn_slab || gs % per16 != 0 || gs > 32) return 0;
-    const int cps = gs / per16;
-    if (cps != 1 && cps != 2 && cps != 4 && cps != 8) return 0;
-    int sh = 0;
-    while ((1 << sh) < cps) ++sh;
-    *cps_shift = sh;
-    return (long)HW * cps;
-}
-unsigned slab_grid(int B) { return 8u * GN_GROUPS * ((B + 7) / 8); }
-// A slab workgroup runs load -> reduce -> apply -> store back to back with the CU to itself (1024 threads), and only B*16
-// of them exist: measured (tools/gn_bench.py, B = 8, bf16) it wins 3x on the 12x40 layers (6.8 vs 19 us forward, 19 vs 37 us
-// backward), ties at 24x80 and loses at 48x160, where the streaming kernels overlap their phases across workgroups.
-constexpr long GN_SLAB_MAX = 1024L * 4;
-
-template <typename T, bool HAS2> bool launch_fwd_slab(const GnArgs& a, long n, hipStream_t st) {
-    const dim3 grid(slab_grid(a.B));
-#define GN_FWD_SLAB(NCH)                                                                                       \
-    if (n <= 1024L * NCH) { hipLaunchKernelGGL((gn_fwd_slab_kernel<T, HAS2, NCH, 1024>), grid, dim3(1024), 0, st, a); return true; }
-    GN_FWD_SLAB(2) GN_FWD_SLAB(4)
-#undef GN_FWD_SLAB
-    return false;
-}
-template <typename T, int HAS2, bool HASDB> bool launch_bwd_slab(const GnArgs& a, long n, hipStream_t st) {
-    const dim3 grid(slab_grid(a.B));
-#define GN_BWD_SLAB(NCH, NT)                                                                                   \
-    if (n <= (long)NT * NCH) { hipLaunchKernelGGL((gn_bwd_slab_kernel<T, HAS2, HASDB, NCH, NT>), grid, dim3(NT), 0, st, a); return true; }
-    GN_BWD_SLAB(2, 1024) GN_BWD_SLAB(4, 1024)
-#undef GN_BWD_SLAB
-    return false;
-}
-
-int g_gn_cluster = 1;                               // development knob (mte_debug_set(25, v)): 0 = no cluster kernels
-void gn_common(GnArgs& a) { a.err = g_mte_err_dev; a.fences = g_mte_handoff_fences; a.spin_max = g_gn_spin_max; }
-
-// cluster geometry for a slab of n chunks that is too large for the slab kernels: CL workgroups of 256 threads, NCH chunks per thread.
-// regs = 16-byte registers a thread holds per chunk (forward: 1 + second input; backward: 2 + second input).  0 = not a cluster shape.
-int cluster_plan(int B, int HW, int C, long n, int sh, int regs, int* nch, int* per_launch) {
-    if (!g_gn_cluster || n <= GN_SLAB_MAX || B < 1) return 0;
-    const int slots = MTE_GN_SLOTS(B);
-    // the registers decide the workgroups per slab: <= 128 VGPRs without spills (measured on the compiler's report) = 12 sixteen-byte data
-    // registers per thread, so four workgroups per CU stay resident
-    int nmax = 8;
-    while (nmax * regs > 12) nmax >>= 1;
-    if (nmax < 2) return 0;
-    // (measured, tools/gn_bench.py: clusters of 16 with the batch in two launches of 4 samples -- 256 channels at 48x160 backward, 128 at 96x320
-    //  forward -- run 1.4-2.3x SLOWER than the streaming kernels: 66 vs 48 us, 89 vs 38 us; a cluster pays only when ONE launch of <= 8
-    //  workgroups per slab covers 8 samples)
-    int cl = 2;
-    while (cl < 8 && ((long)((HW + cl - 1) / cl) << sh) > 256L * nmax) cl <<= 1;
-    const long per_wg = (long)((HW + cl - 1) / cl) << sh;  // chunks of the largest pixel range
-    if (per_wg > 256L * nmax || 2 + 2 * cl > slots * 2) return 0;
-    int n_ = 2;
-    while (256L * n_ < per_wg) n_ <<= 1;
-    *nch = n_;
-    // every LIVE workgroup of a launch must be resident (1024 of 256 threads): samples per launch; the batch goes out in several launches
-    const int pl = 8;                                      // (the block map would also deal 4, 2 or 1 samples to the 8 XCD labels)
-    if (pl * GN_GROUPS * cl > 1024) return 0;
-    if ((B + pl - 1) / pl > 4) return 0;                   // more than four launches: the streaming kernels are the better form
-    *per_launch = pl;
-    return cl;
-}
-
-template <typename T, bool HAS2, int CL> bool launch_fwd_cluster_cl(GnArgs a, int nch, int per_launch, hipStream_t st) {
-    const dim3 grid((unsigned)(per_launch * GN_GROUPS * CL));
-    a.ppl = per_launch;
-#define GN_FWD_CL(NCH) if (nch == NCH) { if constexpr (NCH * (HAS2 ? 2 : 1) <= 12) { \
-        for (a.b0 = 0; a.b0 < a.B; a.b0 += per_launch) { a.nb = a.B - a.b0 < per_launch ? a.B - a.b0 : per_launch;          \
-            hipLaunchKernelGGL((gn_fwd_cluster_kernel<T, HAS2, NCH, CL>), grid, dim3(256), 0, st, a); }                      \
-        return true; } }
-    GN_FWD_CL(2) GN_FWD_CL(4) GN_FWD_CL(8)
-#undef GN_FWD_CL
-    return false;
-}
-template <typename T, bool HAS2> bool launch_fwd_cluster(const GnArgs& a, int cl, int nch, int per_launch, hipStream_t st) {
-    if (cl == 16) return launch_fwd_cluster_cl<T, HAS2, 16>(a, nch, per_launch, st);
-    if (cl == 8) return launch_fwd_cluster_cl<T, HAS2, 8>(a, nch, per_launch, st);
-    if (cl == 4) return launch_fwd_cluster_cl<T, HAS2, 4>(a, nch, per_launch, st);
-    if (cl == 2) return launch_fwd_cluster_cl<T, HAS2, 2>(a, nch, per_launch, st);
-    return false;
-}
-template <typename T, int HAS2, bool HASDB, int CL> bool launch_bwd_cluster_cl(GnArgs a, int nch, int per_launch, hipStream_t st) {
-    const dim3 grid((unsigned)(per_launch * GN_GROUPS * CL));
-    a.ppl = per_launch;
-#define GN_BWD_CL(NCH) if (nch == NCH) { if constexpr (NCH * (HAS2 == 1 ? 3 : 2) <= 12) { \
-        for (a.b0 = 0; a.b0 < a.B; a.b0 += per_launch) { a.nb = a.B - a.b0 < per_launch ? a.B - a.b0 : per_launch;          \
-            hipLaunchKernelGGL((gn_bwd_cluster_kernel<T, HAS2, HASDB, NCH, CL>), grid, dim3(256), 0, st, a); }               \
-        return true; } }
-    GN_BWD_CL(2) GN_BWD_CL(4)
-#undef GN_BWD_CL
-    return false;
-}
-template <typename T, int HAS2, bool HASDB> bool launch_bwd_cluster(const GnArgs& a, int cl, int nch, int per_launch, hipStream_t st) {
-    if (cl == 16) return launch_bwd_cluster_cl<T, HAS2, HASDB, 16>(a, nch, per_launch, st);
-    if (cl == 8) return launch_bwd_cluster_cl<T, HAS2, HASDB, 8>(a, nch, per_launch, st);
-    if (cl == 4) return launch_bwd_cluster_cl<T, HAS2, HASDB, 4>(a, nch, per_launch, st);
-    if (cl == 2) return launch_bwd_cluster_cl<T, HAS2, HASDB, 2>(a, nch, per_launch, st);
-    return false;
-}
+GnKnobs g_gn_knobs;                                 // development knobs (mte_debug_set(2 / 3 / 13 / 14 / 25, v) -> mtei_set_gn)
 
 // statistics from per-tile records (round 5: the LDS-patch forward kernels leave one record of 32 floats per output tile, conv_patch.hip: patch_gn_record):
 // stats[b][group][2] (fp64) = the records of sample b added in tile order.  One workgroup per sample; 32 threads per value take tiles k, k + 32, ... in order,
@@ -1069,134 +950,123 @@ __global__ __launch_bounds__(1024) void gn_stats_from_records_kernel(const float
     }
 }
 
-template <typename T> int run_stats(GnArgs& a, hipStream_t stream) {
-    constexpr int NT = 1024;
-    const int rstep = NT / (a.C / Elem<T>::PER16);
-    // the same number of threads as 2048 workgroups of 256 would be; one record slot per block
-    long want = ((long)g_gn_target * 256 / NT + a.B - 1) / a.B;
-    const int min_rows = g_gn_min_rows < 16 ? g_gn_min_rows : 16;
-    const long maxb = ((long)a.HW + (long)min_rows * rstep - 1) / ((long)min_rows * rstep);
-    if (want > maxb) want = maxb;
-    if (want > MTE_GN_SLOTS(a.B)) want = MTE_GN_SLOTS(a.B);
-    a.blocks_per_sample = (int)(want < 1 ? 1 : want);
-    a.reverse = g_gn_zigzag;                               // the producing conv wrote sample 0 first: start on the freshest bytes
-    dim3 grid(a.blocks_per_sample, a.B);
-    if (a.y2) hipLaunchKernelGGL((gn_stats_kernel<T, true, NT>), grid, dim3(NT), 0, stream, a);
-    else hipLaunchKernelGGL((gn_stats_kernel<T, false, NT>), grid, dim3(NT), 0, stream, a);
-    return mte_check_launch();
+// launch i of the plan with kernel K; a cluster form goes out once per per_launch samples
+template <auto K> void gn_go(const GnPlan& pl, int i, GnArgs a, hipStream_t st, int& sent) {
+    const GnLaunch& l = pl.launch[i];
+    a.reverse = l.reverse;
+    for (int j = 0; j < pl.launches; ++j, ++sent) {
+        if (pl.per_launch) { a.b0 = j * pl.per_launch; a.nb = a.B - a.b0 < pl.per_launch ? a.B - a.b0 : pl.per_launch; }
+        hipLaunchKernelGGL(K, dim3(l.grid_x, l.grid_y), dim3(l.block), l.lds, st, a);
+    }
+}
+#define GN_GO(i, ...) gn_go<__VA_ARGS__>(pl, i, a, st, sent)
+// GN_CLUSTERS(kernel<...): kernel<..., NCH, CL> of the plan's chunks per thread and cluster size (NCH8: whether the instance with eight chunks exists)
+#define GN_CLUSTER(CL_, ...)                                                                                                       \
+    case CL_: if (pl.NCH == 2) GN_GO(0, __VA_ARGS__, 2, CL_>); else if (pl.NCH == 4) GN_GO(0, __VA_ARGS__, 4, CL_>);               \
+              else if constexpr (NCH8) { if (pl.NCH == 8) GN_GO(0, __VA_ARGS__, 8, CL_>); }                                        \
+              break;
+#define GN_CLUSTERS(...) switch (pl.CL) { GN_CLUSTER(16, __VA_ARGS__) GN_CLUSTER(8, __VA_ARGS__) GN_CLUSTER(4, __VA_ARGS__) GN_CLUSTER(2, __VA_ARGS__) }
+
+// A run-time choice as a type, each written once: f(T) for the element type, f(bool constant), f(M2) for the second-tensor mode of the backward kernels
+// (see gn_elu_bwd_apply_kernel: 1 = second input tensor, 2 = one input whose gradient also leaves scaled)
+template <typename F> void gn_by_type(const GnProblem& p, F f) { if (p.elem_size == 2) f(bf16_t{}); else f(float{}); }
+template <typename F> void gn_by_bool(bool v, F f) { if (v) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> void gn_by_second(GnSecond s, F f) {
+    if (s == GnSecond::Input) f(std::integral_constant<int, 1>{});
+    else if (s == GnSecond::ScaledOutput) f(std::integral_constant<int, 2>{});
+    else f(std::integral_constant<int, 0>{});
 }
 
-template <typename T> int run_fwd(GnArgs& a, hipStream_t stream, int reverse = 0) {
-    a.blocks_per_sample = gn_blocks(a.B, a.HW, 256 / (a.C / Elem<T>::PER16), true);
-    a.reverse = reverse;                                   // ... and the statistics pass ended on sample 0
-    dim3 grid(a.blocks_per_sample, a.B);
-    if (a.y2) hipLaunchKernelGGL((gn_elu_fwd_kernel<T, true>), grid, dim3(256), 0, stream, a);
-    else hipLaunchKernelGGL((gn_elu_fwd_kernel<T, false>), grid, dim3(256), 0, stream, a);
+// Plans the pass and launches the plan: the clears it asks for (unless the caller pre-zeroed), then a switch from the plan to the template instance
+// (the instances are named pass by pass in the order the host code named them before gn_plan.hpp: the compiler emits the kernels in that order, and the code
+//  it generates for twenty of the fp32 ones -- operand order of packed adds -- follows the module's function order, profiles/gn_plan_refactor.txt)
+int launch_gn(const GnProblem& p, GnArgs a, hipStream_t st) {
+    const GnPlan pl = plan_gn(p, g_gn_knobs);
+    if (pl.rc != MTE_OK) return pl.rc;
+    const unsigned clears = g_mte_gn_prezeroed ? 0u : pl.clears;
+    auto clear = [&](unsigned which, void* ptr, size_t bytes) { return !(clears & which) || mte_memset_async(ptr, 0, bytes, st) == hipSuccess; };
+    if (!clear(GN_CLEAR_RED, a.red, sizeof(float) * (size_t)a.B * a.C * 2) || !clear(GN_CLEAR_DBIAS, a.dbias, sizeof(float) * a.C) ||
+        !clear(GN_CLEAR_DGAMMA_DBETA, a.dgamma, sizeof(float) * a.C) || !clear(GN_CLEAR_DGAMMA_DBETA, a.dbeta, sizeof(float) * a.C) ||
+        !clear(GN_CLEAR_TICKETS, mte_gn_tickets(a.stats, a.B), sizeof(double) * ((a.B + 15) & ~15)) ||
+        !clear(GN_CLEAR_RECORDS, mte_gn_partials(a.stats, a.B), sizeof(double) * (size_t)a.B * MTE_GN_SLOTS(a.B) * 32)) return MTE_ERR_LAUNCH;
+    a.err = g_mte_err_dev; a.fences = g_mte_handoff_fences; a.spin_max = g_gn_knobs.spin_max;
+    a.blocks_per_sample = pl.blocks_per_sample; a.cps_shift = pl.cps_shift; a.ppl = pl.per_launch;
+    const bool two = p.second == GnSecond::Input;
+    int sent = 0;
+    switch (p.pass) {
+    case GnPass::Stats:
+        gn_by_type(p, [&](auto t) { gn_by_bool(two, [&](auto h2) { GN_GO(0, gn_stats_kernel<decltype(t), decltype(h2)::value, 1024>); }); });
+        break;
+    case GnPass::FwdSingle:
+        if (pl.form == GnForm::Cluster)
+            gn_by_type(p, [&](auto t) { gn_by_bool(two, [&](auto h2) {
+                constexpr bool HAS2 = decltype(h2)::value, NCH8 = !HAS2;      // (eight chunks and a second input: 16 registers, no such instance)
+                GN_CLUSTERS(gn_fwd_cluster_kernel<decltype(t), HAS2)
+            }); });
+        else
+            gn_by_type(p, [&](auto t) { gn_by_bool(two, [&](auto h2) {
+                if (pl.NCH == 2) GN_GO(0, gn_fwd_slab_kernel<decltype(t), decltype(h2)::value, 2, 1024>);
+                else if (pl.NCH == 4) GN_GO(0, gn_fwd_slab_kernel<decltype(t), decltype(h2)::value, 4, 1024>);
+            }); });
+        break;
+    case GnPass::FwdApply:
+        gn_by_type(p, [&](auto t) { gn_by_bool(two, [&](auto h2) { GN_GO(0, gn_elu_fwd_kernel<decltype(t), decltype(h2)::value>); }); });
+        break;
+    case GnPass::Bwd:
+        gn_by_type(p, [&](auto t) {
+            using T = decltype(t);
+            if (pl.form == GnForm::Slab)
+                gn_by_second(p.second, [&](auto m2) { gn_by_bool(p.dbias, [&](auto db) {
+                    constexpr int M2 = decltype(m2)::value;
+                    if constexpr (M2 != 2) {                 // (a scaled second output never takes a slab: no such instance)
+                        if (pl.NCH == 2) GN_GO(0, gn_bwd_slab_kernel<T, M2, decltype(db)::value, 2, 1024>);
+                        else if (pl.NCH == 4) GN_GO(0, gn_bwd_slab_kernel<T, M2, decltype(db)::value, 4, 1024>);
+                    }
+                }); });
+            else if (pl.form == GnForm::Cluster)
+                gn_by_second(p.second, [&](auto m2) { gn_by_bool(p.dbias, [&](auto db) {
+                    constexpr bool NCH8 = false;
+                    GN_CLUSTERS(gn_bwd_cluster_kernel<T, decltype(m2)::value, decltype(db)::value)
+                }); });
+            else
+                gn_by_second(p.second, [&](auto m2) { gn_by_bool(p.dbias, [&](auto db) {
+                    GN_GO(0, gn_elu_bwd_reduce_kernel<T, decltype(m2)::value == 1>);
+                    GN_GO(1, gn_elu_bwd_apply_kernel<T, decltype(m2)::value, decltype(db)::value>);
+                }); });
+        });
+        break;
+    case GnPass::TailStats:
+        gn_by_type(p, [&](auto t) { GN_GO(0, gn_stats_kernel<decltype(t), true, 1024, true>); });
+        break;
+    }
+    if (sent != pl.kernels * pl.launches) return MTE_ERR_UNSUPPORTED;      // (a plan without an instance: plan_gn names none, tests/test_gn_launch_table_cpu.py)
     return mte_check_launch();
 }
+#undef GN_CLUSTERS
+#undef GN_CLUSTER
+#undef GN_GO
 
-template <typename T> int run_bwd(GnArgs& a, int dtype, hipStream_t stream) {
-    int sh = 0;
-    const long n = slab_chunks(a.HW, a.C, dtype, &sh);
-    // second-output mode (see gn_elu_bwd_apply_kernel): 1 = second input tensor, 2 = one input whose gradient also leaves scaled (d2 = scale2 * d1)
-    const int m2 = a.y2 ? 1 : (a.scale2 && a.d2 ? 2 : 0);
-    if (m2 != 1) a.y2 = nullptr;
-    if (m2 == 0) { a.scale2 = nullptr; a.d2 = nullptr; }
-    if (n > 0 && n <= GN_SLAB_MAX && m2 != 2) {
-        a.cps_shift = sh;
-        // the slab kernels ADD this sample's part of dgamma / dbeta (the stream kernels overwrite them): clear them first (prezeroed callers did)
-        if (!g_mte_gn_prezeroed && (mte_memset_async(a.dgamma, 0, sizeof(float) * a.C, stream) != hipSuccess ||
-                                    mte_memset_async(a.dbeta, 0, sizeof(float) * a.C, stream) != hipSuccess)) return MTE_ERR_LAUNCH;
-        bool done;
-        if (a.y2) done = a.dbias ? launch_bwd_slab<T, 1, true>(a, n, stream) : launch_bwd_slab<T, 1, false>(a, n, stream);
-        else if (a.dbias) done = launch_bwd_slab<T, 0, true>(a, n, stream);
-        else done = launch_bwd_slab<T, 0, false>(a, n, stream);
-        if (done) return mte_check_launch();
-    }
-    if (n > GN_SLAB_MAX) {                  // (round 5: also the tail with a bias gradient -- the kernels scale the column sums now)
-        int nch = 0, pl = 0;
-        const int cl = cluster_plan(a.B, a.HW, a.C, n, sh, a.y2 ? 3 : 2, &nch, &pl);
-        if (cl) {
-            a.cps_shift = sh;
-            if (!g_mte_gn_prezeroed && (mte_memset_async(a.dgamma, 0, sizeof(float) * a.C, stream) != hipSuccess ||
-                                        mte_memset_async(a.dbeta, 0, sizeof(float) * a.C, stream) != hipSuccess)) return MTE_ERR_LAUNCH;
-            bool done;
-            if (a.y2) done = a.dbias ? launch_bwd_cluster<T, 1, true>(a, cl, nch, pl, stream) : launch_bwd_cluster<T, 1, false>(a, cl, nch, pl, stream);
-            else if (m2 == 2) done = a.dbias ? launch_bwd_cluster<T, 2, true>(a, cl, nch, pl, stream) : launch_bwd_cluster<T, 2, false>(a, cl, nch, pl, stream);
-            else if (a.dbias) done = launch_bwd_cluster<T, 0, true>(a, cl, nch, pl, stream);
-            else done = launch_bwd_cluster<T, 0, false>(a, cl, nch, pl, stream);
-            if (done) return mte_check_launch();
-        }
-    }
-    a.blocks_per_sample = gn_blocks(a.B, a.HW, 256 / (a.C / Elem<T>::PER16));
-    dim3 grid(a.blocks_per_sample, a.B);
-    const size_t lds = sizeof(float) * a.C * 2;
-    GnArgs a2 = a;
-    a2.reverse = g_gn_zigzag;                              // the apply pass starts where the reduce pass ended
-    const size_t ldb = a.dbias ? sizeof(float) * a.C : 0;
-    if (a.y2) {
-        hipLaunchKernelGGL((gn_elu_bwd_reduce_kernel<T, true>), grid, dim3(256), lds, stream, a);
-        if (a.dbias) hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 1, true>), grid, dim3(256), ldb, stream, a2);
-        else hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 1, false>), grid, dim3(256), 0, stream, a2);
-    } else {
-        hipLaunchKernelGGL((gn_elu_bwd_reduce_kernel<T, false>), grid, dim3(256), lds, stream, a);
-        if (m2 == 2) {
-            if (a.dbias) hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 2, true>), grid, dim3(256), ldb, stream, a2);
-            else hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 2, false>), grid, dim3(256), 0, stream, a2);
-        } else if (a.dbias) hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 0, true>), grid, dim3(256), ldb, stream, a2);
-        else hipLaunchKernelGGL((gn_elu_bwd_apply_kernel<T, 0, false>), grid, dim3(256), 0, stream, a2);
-    }
-    return mte_check_launch();
-}
-
-// the residual tail's first kernel (gn_stats_kernel<.., TAIL>): the geometry of the statistics pass
-template <typename T> int run_tail(GnArgs& a, hipStream_t stream) {
-    constexpr int NT = 1024;
-    const int rstep = NT / (a.C / Elem<T>::PER16);
-    long want = ((long)g_gn_target * 256 / NT + a.B - 1) / a.B;
-    const int min_rows = g_gn_min_rows < 16 ? g_gn_min_rows : 16;
-    const long maxb = ((long)a.HW + (long)min_rows * rstep - 1) / ((long)min_rows * rstep);
-    if (want > maxb) want = maxb;
-    if (want > MTE_GN_SLOTS(a.B)) want = MTE_GN_SLOTS(a.B);
-    a.blocks_per_sample = (int)(want < 1 ? 1 : want);
-    a.reverse = 0;                                         // the inner layer's statistics pass ended on sample 0
-    dim3 grid(a.blocks_per_sample, a.B);
-    hipLaunchKernelGGL((gn_stats_kernel<T, true, NT, true>), grid, dim3(NT), 0, stream, a);
-    return mte_check_launch();
-}
+int gn_elem_size(int dtype) { return dtype == MTE_DT_BF16 ? 2 : 4; }
 
 }  // namespace
 
 #ifdef MTE_DEV
-extern "C" int mtei_set_gn(int which, int value) {
-    if (which == 2) { g_gn_slab = value; return MTE_OK; }
-    if (which == 3) { g_gn_zigzag = value; return MTE_OK; }
-    if (which == 4) { if (value >= 1000) g_gn_spin_max = (unsigned)(value - 1000); else g_gn_cluster = value; return MTE_OK; }
-    if (value < 1) return MTE_ERR_ARG;
-    if (which == 0) g_gn_min_rows = value; else g_gn_target = value;
-    return MTE_OK;
-}
+extern "C" int mtei_set_gn(int key, int value) { return gn_knob_set(g_gn_knobs, key, value); }
 #endif
 
 extern "C" {
 
-// 1 if mte_gn_elu_fwd computes the statistics of this shape itself (single-pass slab kernel): the caller then skips mte_gn_stats.
+// 1 if mte_gn_elu_fwd computes the statistics of this shape itself in a single-pass slab kernel, whatever the batch: the caller then skips mte_gn_stats.
 int mte_gn_fwd_is_single_pass(int HW, int C, int has_y2, int dtype) {
-    int sh = 0;
-    if (!gn_shape_ok(C, dtype)) return 0;
-    const long n = slab_chunks(HW, C, dtype, &sh);
-    return (n > 0 && n <= GN_SLAB_MAX) ? 1 : 0;
+    const GnProblem p{gn_elem_size(dtype), 1, HW, C, GnPass::FwdSingle, has_y2 ? GnSecond::Input : GnSecond::None, false, false};
+    return plan_gn(p, g_gn_knobs).form == GnForm::Slab ? 1 : 0;
 }
 
 // The same question for a batch of B samples: also 1 where a cluster of workgroups holds the slab (norm_act.hip, CLUSTER kernels; the
-// cluster's size depends on the batch).  Callers that know B ask this one.
+// cluster's size depends on the batch).  Callers that know B ask this one.  The plan mte_gn_elu_fwd launches is the one asked here.
 int mte_gn_fwd_is_single_pass_b(int B, int HW, int C, int has_y2, int dtype) {
-    int sh = 0, nch = 0, pl = 0;
-    if (!gn_shape_ok(C, dtype)) return 0;
-    const long n = slab_chunks(HW, C, dtype, &sh);
-    if (n <= 0) return 0;
-    if (n <= GN_SLAB_MAX) return 1;
-    return cluster_plan(B, HW, C, n, sh, has_y2 ? 2 : 1, &nch, &pl) ? 1 : 0;
+    const GnProblem p{gn_elem_size(dtype), B, HW, C, GnPass::FwdSingle, has_y2 ? GnSecond::Input : GnSecond::None, false, false};
+    return gn_single_pass(plan_gn(p, g_gn_knobs)) ? 1 : 0;
 }
 
 // doubles of a statistics buffer for batch B (final sums + arrival tickets + per-block records, see common.hpp)
@@ -1207,11 +1077,9 @@ long mte_gn_stats_elems(int B) { return B < 1 ? 0 : mte_gn_stats_elems_(B); }
 int mte_gn_stats(const void* y1, long ld1, const void* y2, long ld2, const float* scale2, double* stats,
                  int B, int HW, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!y1 || !stats || !gn_shape_ok(C, dtype)) return MTE_ERR_ARG;
-    if (!g_mte_gn_prezeroed && mte_memset_async(mte_gn_tickets(stats, B), 0, sizeof(double) * ((B + 15) & ~15), stream) != hipSuccess) return MTE_ERR_LAUNCH;
+    if (!y1 || !stats) return MTE_ERR_ARG;
     GnArgs a{}; a.y1 = y1; a.ld1 = ld1; a.y2 = y2; a.ld2 = ld2; a.scale2 = scale2; a.stats = stats; a.B = B; a.HW = HW; a.C = C;
-    gn_common(a);
-    return dtype == MTE_DT_BF16 ? run_stats<bf16_t>(a, stream) : run_stats<float>(a, stream);
+    return launch_gn({gn_elem_size(dtype), B, HW, C, GnPass::Stats, y2 ? GnSecond::Input : GnSecond::None, false, false}, a, stream);
 }
 
 int mte_gn_stats_from_records(const float* rec, int tiles_per_sample, double* stats, int B, hipStream_t stream) {
@@ -1222,37 +1090,16 @@ int mte_gn_stats_from_records(const float* rec, int tiles_per_sample, double* st
 }
 
 // z = ELU(GN(y1 + scale2*y2)).  stats: the sums mte_gn_stats (or a conv epilogue) accumulated -- or, where
-// mte_gn_fwd_is_single_pass(HW, C, y2 != null, dtype) is 1 and stats_ready == 0, an OUTPUT: the kernel computes the
+// mte_gn_fwd_is_single_pass_b(B, HW, C, y2 != null, dtype) is 1 and stats_ready == 0, an OUTPUT: the kernel computes the
 // statistics of the slab it holds on chip and stores them in the same format for the backward pass.
 int mte_gn_elu_fwd(const void* y1, long ld1, const void* y2, long ld2, const float* scale2, double* stats, int stats_ready,
                    const float* gamma, const float* beta, void* z, long ldz,
                    int B, int HW, int C, float eps, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!y1 || !stats || !gamma || !beta || !z || !gn_shape_ok(C, dtype)) return MTE_ERR_ARG;
+    if (!y1 || !stats || !gamma || !beta || !z) return MTE_ERR_ARG;
     GnArgs a{}; a.y1 = y1; a.ld1 = ld1; a.y2 = y2; a.ld2 = ld2; a.scale2 = scale2; a.stats = stats;
     a.gamma = gamma; a.beta = beta; a.z = z; a.ldz = ldz; a.B = B; a.HW = HW; a.C = C; a.eps = eps;
-    gn_common(a);
-    if (!stats_ready) {
-        if (!mte_gn_fwd_is_single_pass_b(B, HW, C, y2 != nullptr, dtype)) return MTE_ERR_ARG;
-        int sh = 0;
-        const long n = slab_chunks(HW, C, dtype, &sh);
-        a.cps_shift = sh;
-        bool ok;
-        if (n > GN_SLAB_MAX) {                             // a cluster of workgroups per (sample, group)
-            int nch = 0, pl = 0;
-            const int cl = cluster_plan(B, HW, C, n, sh, y2 ? 2 : 1, &nch, &pl);
-            // the cluster's exchange words live in the record area of the statistics buffer and must be zero at entry
-            if (!g_mte_gn_prezeroed &&
-                mte_memset_async(mte_gn_partials(stats, B), 0, sizeof(double) * (size_t)B * MTE_GN_SLOTS(B) * 32, stream) != hipSuccess) return MTE_ERR_LAUNCH;
-            if (dtype == MTE_DT_BF16) ok = y2 ? launch_fwd_cluster<bf16_t, true>(a, cl, nch, pl, stream) : launch_fwd_cluster<bf16_t, false>(a, cl, nch, pl, stream);
-            else ok = y2 ? launch_fwd_cluster<float, true>(a, cl, nch, pl, stream) : launch_fwd_cluster<float, false>(a, cl, nch, pl, stream);
-            return ok ? mte_check_launch() : MTE_ERR_ARG;
-        }
-        if (dtype == MTE_DT_BF16) ok = y2 ? launch_fwd_slab<bf16_t, true>(a, n, stream) : launch_fwd_slab<bf16_t, false>(a, n, stream);
-        else ok = y2 ? launch_fwd_slab<float, true>(a, n, stream) : launch_fwd_slab<float, false>(a, n, stream);
-        return ok ? mte_check_launch() : MTE_ERR_ARG;
-    }
-    return dtype == MTE_DT_BF16 ? run_fwd<bf16_t>(a, stream) : run_fwd<float>(a, stream);
+    return launch_gn({gn_elem_size(dtype), B, HW, C, stats_ready ? GnPass::FwdApply : GnPass::FwdSingle, y2 ? GnSecond::Input : GnSecond::None, false, false}, a, stream);
 }
 
 // Backward of z = ELU(GN(y1 + scale2*y2)).  red[B][C][2] is scratch (zeroed here).  Writes d1 (grad of y1),
@@ -1263,17 +1110,14 @@ int mte_gn_elu_bwd(const void* dz, long lddz, const void* y1, long ld1, const vo
                    void* d1, long ldd1, void* d2, long ldd2, float* dgamma, float* dbeta, float* dbias,
                    int B, int HW, int C, float eps, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!dz || !y1 || !stats || !gamma || !beta || !red || !d1 || !dgamma || !dbeta || !gn_shape_ok(C, dtype)) return MTE_ERR_ARG;
+    if (!dz || !y1 || !stats || !gamma || !beta || !red || !d1 || !dgamma || !dbeta) return MTE_ERR_ARG;
     if (d2 && !y2 && !scale2) return MTE_ERR_ARG;      // a second output needs its factor (with one input d2 = scale2 * d1): never MTE_OK with d2 left unwritten
-    if (!g_mte_gn_prezeroed) {
-        if (mte_memset_async(red, 0, sizeof(float) * (size_t)B * C * 2, stream) != hipSuccess) return MTE_ERR_LAUNCH;
-        if (dbias && mte_memset_async(dbias, 0, sizeof(float) * C, stream) != hipSuccess) return MTE_ERR_LAUNCH;
-    }
-    GnArgs a{}; a.dbias = dbias; a.dgamma = dgamma; a.dbeta = dbeta; a.y1 = y1; a.ld1 = ld1; a.y2 = y2; a.ld2 = ld2; a.scale2 = scale2; a.stats = (double*)stats;
-    a.gamma = gamma; a.beta = beta; a.dz = dz; a.lddz = lddz; a.red = red; a.d1 = d1; a.ldd1 = ldd1; a.d2 = d2; a.ldd2 = ldd2;
+    const GnSecond second = y2 ? GnSecond::Input : (scale2 && d2 ? GnSecond::ScaledOutput : GnSecond::None);
+    GnArgs a{}; a.dbias = dbias; a.dgamma = dgamma; a.dbeta = dbeta; a.y1 = y1; a.ld1 = ld1; a.y2 = y2; a.ld2 = ld2; a.stats = (double*)stats;
+    a.gamma = gamma; a.beta = beta; a.dz = dz; a.lddz = lddz; a.red = red; a.d1 = d1; a.ldd1 = ldd1; a.ldd2 = ldd2;
     a.B = B; a.HW = HW; a.C = C; a.eps = eps;
-    gn_common(a);
-    return dtype == MTE_DT_BF16 ? run_bwd<bf16_t>(a, dtype, stream) : run_bwd<float>(a, dtype, stream);
+    if (second != GnSecond::None) { a.scale2 = scale2; a.d2 = d2; }      // (a factor or an output without its partner is not passed on)
+    return launch_gn({gn_elem_size(dtype), B, HW, C, GnPass::Bwd, second, dbias != nullptr, false}, a, stream);
 }
 
 // The residual block's tail, ELU(GN_t(ELU(GN_1(y1)) + scale2 * y2)) (ResidualConv.forward, layers01.py:62-73: y1 = conv2's convolution output,
@@ -1288,17 +1132,13 @@ int mte_gn_tail_fwd(const void* y1, long ld1, const double* stats1, const float*
                     const float* gamma_t, const float* beta_t, void* z, long ldz,
                     int B, int HW, int C, float eps, int dtype, hipStream_t stream) {
     (void)hipGetLastError();
-    if (!y1 || !stats1 || !gamma1 || !beta1 || !y2 || !t || !stats_t || !gamma_t || !beta_t || !z || !gn_shape_ok(C, dtype)) return MTE_ERR_ARG;
-    if (!g_mte_gn_prezeroed && mte_memset_async(mte_gn_tickets(stats_t, B), 0, sizeof(double) * ((B + 15) & ~15), stream) != hipSuccess) return MTE_ERR_LAUNCH;
+    if (!y1 || !stats1 || !gamma1 || !beta1 || !y2 || !t || !stats_t || !gamma_t || !beta_t || !z) return MTE_ERR_ARG;
     GnArgs a{}; a.y1 = y1; a.ld1 = ld1; a.y2 = y2; a.ld2 = ld2; a.scale2 = scale2; a.stats_in = stats1; a.stats = stats_t;
     a.gamma = gamma1; a.beta = beta1; a.z = t; a.ldz = ldt; a.B = B; a.HW = HW; a.C = C; a.eps = eps;
-    gn_common(a);
-    int rc = dtype == MTE_DT_BF16 ? run_tail<bf16_t>(a, stream) : run_tail<float>(a, stream);
+    const int rc = launch_gn({gn_elem_size(dtype), B, HW, C, GnPass::TailStats, GnSecond::Input, false, false}, a, stream);
     if (rc != MTE_OK) return rc;
     GnArgs f{}; f.y1 = t; f.ld1 = ldt; f.stats = stats_t; f.gamma = gamma_t; f.beta = beta_t; f.z = z; f.ldz = ldz; f.B = B; f.HW = HW; f.C = C; f.eps = eps;
-    gn_common(f);
-    rc = dtype == MTE_DT_BF16 ? run_fwd<bf16_t>(f, stream, g_gn_zigzag) : run_fwd<float>(f, stream, g_gn_zigzag);   // (the tail kernel ended on the last sample)
-    return rc;
+    return launch_gn({gn_elem_size(dtype), B, HW, C, GnPass::FwdApply, GnSecond::None, false, true}, f, stream);
 }
 
 int mte_set_option(int option, int value) {

@@ -1,11 +1,13 @@
-"""Launch recorder of the implicit-GEMM convolution: which kernel instance, grid, block and dynamic LDS every case gets, found on the CPU.
+"""Launch recorder of the implicit-GEMM convolution and of GroupNorm: which kernel instance, grid, block and dynamic LDS every case gets, found on the CPU.
 
 conv_igemm.hip and conv_igemm8.hip are compiled for the host alone (hipcc --cuda-host-only) with tests/conv_launch_shim.hpp in front, which turns every launch
 into a line of text, and linked with tests/conv_launch_driver.cpp, which calls the three C entry points.  tests/conv_launch_table.json holds one line per case:
 the case (the driver's input line) and what was launched.  tests/test_conv_launch_table_cpu.py requires the working tree to reproduce every line.
+--gn: the same for norm_act.hip with tests/gn_launch_driver.cpp (four entry points, two queries, the clears) and tests/gn_launch_table.json
+(tests/test_gn_launch_table_cpu.py).
 
-    python tests/conv_launch_recorder.py --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
-    python tests/conv_launch_recorder.py --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+    python tests/conv_launch_recorder.py [--gn] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py [--gn] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
 """
 import argparse
 import json
@@ -18,18 +20,21 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TESTS = os.path.join(ROOT, "tests")
 CSRC = os.path.join(ROOT, "mindtheedge_amd", "csrc")
 TABLE = os.path.join(TESTS, "conv_launch_table.json")
+GN_TABLE = os.path.join(TESTS, "gn_launch_table.json")
 HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
 BF16, F32 = 0, 1
 SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
 
 
-def build(out_dir, dev, csrc=CSRC, extra=()):
-    """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs)"""
-    exe = os.path.join(out_dir, "recorder_dev" if dev else "recorder")
+def build(out_dir, dev, csrc=CSRC, extra=(), gn=False):
+    """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it)"""
+    exe = os.path.join(out_dir, ("gn_" if gn else "") + ("recorder_dev" if dev else "recorder"))
     cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
     cmd += ["-DMTE_DEV"] if dev else []
-    cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip"), os.path.join(TESTS, "conv_launch_driver.cpp"), "-o", exe]
+    cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip")]
+    cmd += [os.path.join(csrc, "norm_act.hip"), os.path.join(TESTS, "gn_launch_driver.cpp")] if gn else [os.path.join(TESTS, "conv_launch_driver.cpp")]
+    cmd += ["-o", exe]
     subprocess.run(cmd, check=True, capture_output=True, text=True)
     return exe
 
@@ -232,15 +237,84 @@ def cases():
     return out
 
 
-def record(csrc=CSRC, dev=True, extra=()):
+# ---- GroupNorm (--gn): (B, C, H, W) of tests/test_gpu_groupnorm.py and tests/test_gpu_handoff_fences.py
+GN_TEST = [(2, 512, 24, 80), (3, 512, 12, 40), (2, 256, 24, 40), (1, 128, 16, 24), (9, 256, 8, 16), (2, 64, 32, 64), (3, 32, 64, 64), (2, 128, 96, 320), (8, 512, 24, 80),
+           (8, 256, 48, 160), (5, 128, 48, 160), (3, 256, 23, 79), (12, 512, 24, 80)]
+GN_TEST_TAIL = [(2, 32, 64, 64), (8, 64, 96, 160), (3, 64, 37, 52), (3, 64, 74, 104)]            # (the tail tests' other shapes are in GN_TEST)
+
+
+def gn_training_shapes():
+    """(B, HW, C) of every GroupNorm of the T8 training step, bench.py's size (PackNetSAN01: ni, n1 .. n5 = 32, 32, 64, 128, 256, 512 at 384 x 1280 and the five
+    halvings below it; these are also the layer classes of tools/gn_bench.py, overlap_probe.py and inloop_clock.py)"""
+    H, W = 384, 1280
+    return [(8, H * W, 32)] + [(8, (H >> i) * (W >> i), c) for i, cs in ((1, (32, 64)), (2, (64, 128)), (3, (128, 256)), (4, (256, 512)), (5, (512,))) for c in cs]
+
+
+def gn_case(entry, dtype, B, HW, C, second=0, dbias=0, ready=0, prezeroed=0, knobs=None):
+    return "%s %d %d %d %d %d %d %d %d %s" % (entry, dtype, B, HW, C, second, dbias, ready, prezeroed, ",".join("%d=%d" % kv for kv in knobs) if knobs else "-")
+
+
+def gn_cases():
+    out = []
+
+    def add(B, HW, C, knobs=None, full=False, single=False, dtypes=(BF16, F32)):
+        """one shape through the entry points.  full: all four, in every combination of the flags each takes.  Otherwise in every combination of what the form and
+        the geometry can depend on -- element type, second tensor, ready statistics -- with the bias gradient on and the buffers not pre-zeroed, i.e. with every
+        clear and the larger dynamic LDS (the whole product over every shape would be four times the convolution table).  single: only the two passes that can
+        take a slab or a cluster, the forward without ready statistics and the backward."""
+        for dtype in dtypes:
+            for pz in (0, 1) if full else (0,):
+                for second in (0, 1):
+                    out.append(gn_case("fwd", dtype, B, HW, C, second, ready=0, prezeroed=pz, knobs=knobs))
+                    if full or (second == 0 and not single):
+                        out.append(gn_case("fwd", dtype, B, HW, C, second, ready=1, prezeroed=pz, knobs=knobs))
+                        out.append(gn_case("stats", dtype, B, HW, C, second, prezeroed=pz, knobs=knobs))
+                    if full or (second == 1 and not single):
+                        out.append(gn_case("tail", dtype, B, HW, C, second, prezeroed=pz, knobs=knobs))
+                for m2 in (0, 1, 2):
+                    for dbias in (0, 1) if full else (1,):
+                        out.append(gn_case("bwd", dtype, B, HW, C, m2, dbias=dbias, prezeroed=pz, knobs=knobs))
+
+    for B, HW, C in gn_training_shapes():                                  # the whole product on one shape of each form: stream, cluster, slab
+        add(B, HW, C, full=(HW, C) in ((96 * 320, 128), (24 * 80, 512), (12 * 40, 512)))
+    for B, C, H, W in GN_TEST:                                             # each with the slab kernels on (the default) and off
+        add(B, H * W, C)
+        add(B, H * W, C, [(13, 0)], single=True)
+    for B, C, H, W in GN_TEST_TAIL:
+        add(B, H * W, C)
+    for B, C, H, W in ((8, 512, 24, 80), (8, 256, 48, 160)):               # test_cluster_route_is_taken_and_is_bit_reproducible
+        add(B, H * W, C, [(25, 0)], single=True, dtypes=(BF16,))
+    add(8, 24 * 80, 512, [(25, 1000)], single=True, dtypes=(BF16,))                        # the spin limit: changes no launch
+    # ---- thresholds.  A slab is HW * cps chunks, cps = chunks per pixel of one group: at C = 512 4 in bf16 and 8 in fp32, at C = 128 1 and 2.
+    for hw in (256, 257, 512, 513, 1024, 1025, 2048, 2049, 4096, 4097):    # C = 512: the slab kernels' NCH step (2048 chunks), GN_SLAB_MAX, the clusters' 4 -> 8
+        add(8, hw, 512, single=True)                                       # and where the cluster rule gives up (256 * nmax chunks per workgroup, nmax = 8 or 4)
+    for hw in (8192, 8193, 16384, 16385):                                  # C = 128: the same steps at one and two chunks per pixel
+        add(8, hw, 128, single=True)
+    for B in (1, 7, 9, 32, 33):                                            # samples per launch: 8; four launches at the most
+        add(B, 24 * 80, 512, single=True)
+    for C in (64, 128, 256, 1024):                                         # group sizes 4 .. 64 channels: cps 1, 2, 4, 8 and no slab (with 8 x 480 x 512 of the step)
+        add(8, 12 * 40, C, single=True)
+    add(8, 24 * 80, 1024, single=True)
+    for C in (24, 48, 2048, 4096):                                         # refused, or refused in fp32 only (2048)
+        add(8, 12 * 40, C)
+    for B in (1, 7, 33):                                                   # the statistics grid: capped by MTE_GN_SLOTS (512, 73 against the 74 wanted, 64)
+        add(B, 20000, 512, dtypes=(BF16,))
+    add(3, 20000, 512, [(3, 1000000)], dtypes=(BF16,))                                     # ... and by 170 slots with a target that asks for more than the rows give
+    for kn in ([(2, 16)], [(2, 17)], [(2, 64)], [(3, 512)], [(3, 8192)], [(14, 0)]):      # min_rows (forward: capped at 16), target, zigzag
+        add(8, 96 * 320, 128, kn, dtypes=(BF16,))
+    seen = set()
+    return [c for c in out if not (c in seen or seen.add(c))]
+
+
+def record(csrc=CSRC, dev=True, extra=(), gn=False):
     with tempfile.TemporaryDirectory() as tmp:
-        cs = cases()
-        return run(build(tmp, dev, csrc, extra), cs if dev else [c for c in cs if c.endswith(" -")])
+        cs = gn_cases() if gn else cases()
+        return run(build(tmp, dev, csrc, extra, gn), cs if dev else [c for c in cs if c.endswith(" -")])
 
 
-def load_table():
+def load_table(path=TABLE):
     """-> the table's lines (the file is a JSON array with one case per line)"""
-    with open(TABLE) as f:
+    with open(path) as f:
         return [line.rstrip(",\n") for line in f if line.startswith("{")]
 
 
@@ -250,10 +324,11 @@ if __name__ == "__main__":
     ap.add_argument("--out")
     ap.add_argument("--write", action="store_true")
     ap.add_argument("--product", action="store_true", help="the build without -DMTE_DEV: the cases that set no knob")
+    ap.add_argument("--gn", action="store_true", help="GroupNorm (norm_act.hip, tests/gn_launch_table.json)")
     a = ap.parse_args()
-    lines = record(a.csrc, dev=not a.product)
+    lines = record(a.csrc, dev=not a.product, gn=a.gn)
     for ln in lines:
         json.loads(ln)
-    with open(TABLE if a.write else a.out, "w") as f:
+    with open((GN_TABLE if a.gn else TABLE) if a.write else a.out, "w") as f:
         f.write("[\n" + ",\n".join(lines) + "\n]\n")
     print("%d cases" % len(lines))

@@ -1,10 +1,12 @@
-// Launch recorder for the implicit-GEMM host code (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip when they are
-// compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute and hipGetLastError are redefined, so no call reaches the HIP runtime: every launch is
-// appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the large-LDS grant the kernel holds at that moment, and
-// for a ConvArgs argument the fields the host chose.
+// Launch recorder for the host code that chooses kernels (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip /
+// norm_act.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
+// call reaches the HIP runtime: every launch is appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the
+// large-LDS grant the kernel holds at that moment, and for a ConvArgs or GnArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
+// kernels of mte_memset_async in common.hpp) is a line of its own: which buffer and how many bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
+#include <stdint.h>
 #include <stdlib.h>
 #include <map>
 #include <typeinfo>
@@ -16,6 +18,8 @@ struct ConvArgs;
 namespace mte_rec {
 inline std::string& log() { static std::string s; return s; }
 inline std::map<const void*, int>& granted() { static std::map<const void*, int> m; return m; }
+// the driver names the buffers it passes (base address -> name); a cleared range is printed as name+offset
+inline std::map<uintptr_t, std::string>& buffers() { static std::map<uintptr_t, std::string> m; return m; }
 
 // typeid(Tag<K>) demangles to "mte_rec::Tag<&(void (anonymous namespace)::conv_igemm_kernel<unsigned short, 2, 2, 2, 2, 2, 4, 1, 0>(ConvArgs))>"; kept of it:
 // "conv_igemm_kernel<unsigned short, 2, 2, 2, 2, 2, 4, 1, 0>"  (__PRETTY_FUNCTION__ of a function templated on the address names the kernel without its arguments)
@@ -26,7 +30,9 @@ template <auto K> std::string kernel_name() {
     std::string s = d ? d : typeid(Tag<K>).name();
     free(d);
     for (size_t at; (at = s.find("(anonymous namespace)::")) != std::string::npos;) s.erase(at, 23);
-    const size_t at = s.find("&(void "), from = at == std::string::npos ? 0 : at + 7;
+    size_t from = s.find("&(");                                             // (a kernel that is no template carries no return type)
+    from = from == std::string::npos ? 0 : from + 2;
+    if (s.compare(from, 5, "void ") == 0) from += 5;
     s = s.substr(from, s.find('(', from) - from);
     for (size_t at; (at = s.find("unsigned short")) != std::string::npos;) s.replace(at, 14, "bf16");
     return s;
@@ -34,20 +40,42 @@ template <auto K> std::string kernel_name() {
 
 inline void field(const char* name, long v, long dflt) { if (v != dflt) log() += std::string(",\"") + name + "\":" + std::to_string(v); }
 
-// (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other ConvArgs fields 0)
-template <typename A> void conv_fields(const A& a) {
+template <typename A, typename = void> struct is_gn_args : std::false_type {};
+template <typename A> struct is_gn_args<A, std::void_t<decltype(A::cps_shift), decltype(A::blocks_per_sample), decltype(A::ppl)>> : std::true_type {};
+
+// (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other fields 0, a pointer null)
+template <typename A> void arg_fields(const A& a) {
     if constexpr (std::is_same_v<A, ConvArgs>) {
         field("splits", a.splits, 1); field("kslice", a.kslice, 0); field("solo", a.solo, 0); field("accum", a.accum, 0); field("unshuffle_c", a.unshuffle_c, 0);
+    } else if constexpr (is_gn_args<A>::value) {
+        field("blocks_per_sample", a.blocks_per_sample, 0); field("reverse", a.reverse, 0); field("cps_shift", a.cps_shift, 0);
+        field("ppl", a.ppl, 0); field("b0", a.b0, 0); field("nb", a.nb, 0);
+        const std::string with = std::string(a.y2 ? " y2" : "") + (a.scale2 ? " scale2" : "") + (a.d2 ? " d2" : "") + (a.dbias ? " dbias" : "");
+        if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";      // the optional pointers that are not null
     }
 }
 
+inline hipError_t clear(const void* p, size_t bytes) {
+    auto it = buffers().upper_bound((uintptr_t)p);
+    std::string name = std::to_string((uintptr_t)p);
+    if (it != buffers().begin()) { --it; name = it->second; if ((uintptr_t)p != it->first) name += "+" + std::to_string((uintptr_t)p - it->first); }
+    log() += std::string(log().empty() ? "" : ",") + "{\"clear\":\"" + name + "\",\"bytes\":" + std::to_string(bytes) + "}";
+    return hipSuccess;
+}
+// the two fill kernels of mte_memset_async: (p, word, 16-byte chunks, tail, tail words) and (p, byte, bytes)
+template <typename... A> bool fill(const A&...) { return false; }
+template <typename P> bool fill(P* const& p, const unsigned&, const size_t& n16, unsigned* const&, const int& ntail) { clear(p, n16 * 16 + (size_t)ntail * 4); return true; }
+inline bool fill(unsigned char* const& p, const unsigned char&, const size_t& n) { clear(p, n); return true; }
+
 template <auto K, typename... A> void launch(dim3 g, dim3 b, size_t lds, hipStream_t, const A&... args) {
+    const std::string name = kernel_name<K>();
+    if (name.compare(0, 8, "mte_fill") == 0 && fill(args...)) return;
     const auto it = granted().find((const void*)K);
-    log() += std::string(log().empty() ? "" : ",") + "{\"k\":\"" + kernel_name<K>() + "\",\"grid\":" + std::to_string(g.x);
+    log() += std::string(log().empty() ? "" : ",") + "{\"k\":\"" + name + "\",\"grid\":" + std::to_string(g.x);
     field("grid_y", g.y, 1); field("grid_z", g.z, 1);
     field("block", b.x, -1); field("block_y", b.y, 1); field("block_z", b.z, 1);
     field("lds", (long)lds, -1); field("granted", it == granted().end() ? 0 : it->second, 0);
-    (conv_fields(args), ...);
+    (arg_fields(args), ...);
     log() += "}";
 }
 inline hipError_t set_attribute(const void* k, hipFuncAttribute, int v) { granted()[k] = v; return hipSuccess; }
@@ -56,4 +84,5 @@ inline hipError_t set_attribute(const void* k, hipFuncAttribute, int v) { grante
 #undef hipLaunchKernelGGL
 #define hipLaunchKernelGGL(kernel, ...) mte_rec::launch<kernel>(__VA_ARGS__)
 #define hipFuncSetAttribute(...) mte_rec::set_attribute(__VA_ARGS__)
+#define hipMemsetAsync(p, value, bytes, stream) mte_rec::clear(p, bytes)
 #define hipGetLastError() hipSuccess
