@@ -13,9 +13,7 @@
 // weights + 4 biases are wave-uniform scalar loads.  These kernels move 2..10 bytes per 27 FMAs: they sit
 // between the HBM and the fp32-VALU roofs, not on MFMA (N = 4 features cannot fill a matrix tile).
 #include "common.hpp"
-#ifndef MTE_P3W_WGS
-#define MTE_P3W_WGS 512      // workgroups of the conv3d weight-gradient launches (side queue; end of round 5, after the kernel's instruction diet, same box: 768 -> 22.00 ms per step, 512 -> 21.94, 384 -> 21.97, 256 -> 22.09)
-#endif
+#include "p3_plan.hpp"
 
 
 namespace {
@@ -451,17 +449,6 @@ __global__ __launch_bounds__(256, 3) void unpack3d_bwd_weight_kernel(P3Args a) {
     block_reduce_atomic(acc, kh, a.dw3, sred);
 }
 
-template <typename KB, typename KF>
-int launch_p3(int dtype, KB kb, KF kf, const P3Args& a, long threads, hipStream_t st, int gy = 1) {
-    const unsigned grid = (unsigned)((threads + 255) / 256);
-    if (dtype == MTE_DT_BF16) hipLaunchKernelGGL(kb, dim3(grid, gy), dim3(256), 0, st, a);
-    else if (dtype == MTE_DT_F32) hipLaunchKernelGGL(kf, dim3(grid, gy), dim3(256), 0, st, a);
-    else return MTE_ERR_UNSUPPORTED;
-    return mte_check_launch();
-}
-
-bool p3_ok(int C) { const int cb = C >> 3; return C % 8 == 0 && cb >= 1 && cb <= 64 && (cb & (cb - 1)) == 0; }
-
 }  // namespace
 
 // =====================================================================================================
@@ -471,27 +458,6 @@ bool p3_ok(int C) { const int cb = C >> 3; return C % 8 == 0 && cb >= 1 && cb <=
 // halo reads, and HBM sees every tensor element about once.  Tile area is chosen so that TH*TW*C = 4096.
 // =====================================================================================================
 namespace {
-
-struct P3Tile { int TH, TW; };
-int g_p3_small_tiles = 1;                            // development knob (mte_debug_set(12, v))
-inline P3Tile p3_tile(int C) {
-    if (g_p3_small_tiles) {
-        if (C <= 32) return {4, 16};
-        if (C <= 64) return {4, 8};
-        if (C <= 128) return {2, 8};
-        if (C <= 256) return {2, 4};
-        return {2, 2};
-    }
-    if (C <= 32) return {8, 16};
-    if (C <= 64) return {4, 16};
-    if (C <= 128) return {4, 8};
-    if (C <= 256) return {2, 8};
-    return {2, 4};
-}
-// LDS tiles keep 8 pad elements (16 B) after the D depths of every pixel: with a power-of-two pixel stride the 16-byte window
-// reads of a wave (64..1024 B apart) fall on a few banks only -- SQ_LDS_BANK_CONFLICT was 47-84 % of the LDS-active cycles.
-#define LDP(D) ((D) + 8)
-inline size_t p3_lds_bytes(int C) { P3Tile t = p3_tile(C); return (size_t)(t.TH + 2) * (t.TW + 2) * LDP(4 * C) * 2; }
 
 struct P3LArgs {
     const bf16_t* x; long ldx;         // un-packed side [B,H,W,C]
@@ -750,15 +716,6 @@ __global__ __launch_bounds__(256) void pack3d_bwd_weight_lds_kernel(P3LArgs a) {
 // ---- LDS-tiled UNPACK backward.  Volume = x [B,H,W,C] (depth = channel).  The feature side is the pixel-shuffled
 // gradient dout [B,2H,2W,C]: feature plane f of the volume is the space-to-depth of dout's channels [f*C/4, (f+1)*C/4),
 // so staging it is stage_packed_tile with (x := dout + f*C/4, C := C/4, H := 2H, W := 2W).
-inline P3Tile up_tile(int C) {                       // TH*TW*C = 16384 (2 items of 32 depths per thread)
-    if (C <= 32) return {16, 32};
-    if (C <= 64) return {8, 32};
-    if (C <= 128) return {8, 16};
-    if (C <= 256) return {4, 16};
-    return {4, 8};
-}
-inline size_t up_lds_bytes(int C) { P3Tile t = up_tile(C); return (size_t)(t.TH + 2) * (t.TW + 2) * LDP(C) * 2; }
-
 __device__ __forceinline__ void up_tile_coords(const P3LArgs& a, int tile, int& b, int& h0, int& w0) {
     const int tw = tile % a.tiles_w; int t = tile / a.tiles_w;
     const int th = t % a.tiles_h; b = t / a.tiles_h;
@@ -825,13 +782,6 @@ __global__ __launch_bounds__(256) void unpack3d_bwd_data_lds_kernel(P3LArgs a) {
 // block comes back for the next plane the record has left L2 -- measured 3.4 GB fetched per step for 0.49 GB of dout.
 // The x-tile is four times smaller instead (TH*TW*C = 4096, one 16-depth item per thread) so the four planes fit the
 // same ~46-61 KB of LDS.
-inline P3Tile up4_tile(int C) {
-    if (C <= 32) return {8, 16};
-    if (C <= 64) return {4, 16};
-    return {4, 8};
-}
-inline size_t up4_lds_bytes(int C) { P3Tile t = up4_tile(C); return (size_t)4 * (t.TH + 2) * (t.TW + 2) * LDP(C) * 2; }
-
 __global__ __launch_bounds__(256) void unpack3d_bwd_data_lds4_kernel(P3LArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem_[];
     bf16_t* tile = (bf16_t*)smem_;
@@ -892,9 +842,6 @@ __global__ __launch_bounds__(256) void unpack3d_bwd_data_lds4_kernel(P3LArgs a) 
 //
 // unpack backward data, C = 32 / 64: tile = TH x 16 pixels, the four feature planes of the pixel-shuffled gradient staged together
 // ([plane][pixel][8 zero | C depths | 8 zero] bf16, 69 KB: two workgroups per CU); a wave owns 4 (tile row, depth block) units.
-int g_p3_tr_passes = 4;                              // development knob (mte_debug_set(1, 3000 + v), v = 1 / 2 / 4): output passes of unpack3d_fwd_tr_kernel
-int g_p3_persist_wgs = 1024;                         // development knob (mte_debug_set(1, 2000 + v)): workgroups of the persistent matrix-core conv3d kernels
-int g_p3_mfma_data = 239;                             // development knob (mte_debug_set(1, 300 + v)): bit 0 = unpack backward data on the matrix cores, bit 1 = its LDS-DMA form for C = 32, bit 2 = 4 waves per workgroup there (0: 2 waves x 4 rows, measured slower), bit 3 = unpack forward on the matrix cores, bit 4 = conv3d weights as ONE bf16 value (no lo part: half the MFMAs), bit 5 = unpack forward with the spatial taps in K (third form), bit 6 = pack forward in that form, bit 7 = pack backward data on the matrix cores (round 6)
 
 __device__ __forceinline__ bf16x8_t banded_fragment(unsigned t0, unsigned t1, const unsigned sel[4]) {
     u32x4_t r;
@@ -1816,37 +1763,98 @@ __global__ __launch_bounds__(512) void conv3d_bwd_weight_mfma_kernel(P3LArgs a) 
     }
 }
 
-inline P3LArgs upl_args(int B, int H, int W, int C, bool half_tile = false) {
-    P3LArgs a{}; a.B = B; a.H = H; a.W = W; a.C = C;
-    P3Tile t = up_tile(C);
-    if (half_tile && t.TH >= 4) t.TH /= 2;               // kernels with generic item loops: half the LDS, twice the resident blocks
-    a.TH = t.TH; a.TW = t.TW;
-    a.tiles_h = (H + t.TH - 1) / t.TH; a.tiles_w = (W + t.TW - 1) / t.TW; a.ntiles = a.tiles_h * a.tiles_w * B;
-    return a;
-}
+P3Knobs g_pack3d_knobs;                             // development knobs (mte_debug_set(1, v), and key 33 as v = P3_KNOB_RESET -> mtei_set_pack3d_lds)
 
-template <auto KF> int launch_p3l(P3LArgs a, int grid, hipStream_t st, size_t lds_override = 0, int threads = 256) {
-    const size_t lds = lds_override ? lds_override : p3_lds_bytes(a.C);
-    if (mte_allow_lds<KF>(112 * 1024) != MTE_OK) return MTE_ERR_LAUNCH;
-    hipLaunchKernelGGL(KF, dim3(grid), dim3(threads), lds, st, a);
+// the gather kernels take the entry point's P3Args as they are
+template <auto K> int launch_gather(const P3Plan& pl, const P3Args& a, hipStream_t st) {
+    hipLaunchKernelGGL(K, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), 0, st, a);
+    return mte_check_launch();
+}
+// every other form: the same pointers as bf16 in a P3LArgs, with the plan's tile geometry
+template <auto K> int launch_tiled(const P3Plan& pl, const P3Args& a, hipStream_t st) {
+    P3LArgs l{};
+    l.x = (const bf16_t*)a.x; l.ldx = a.ldx; l.o = (const bf16_t*)a.o; l.ldo = a.ldo; l.dst = (bf16_t*)a.dst; l.lddst = a.lddst;
+    l.w3 = a.w3; l.b3 = a.b3; l.dwb = a.dw3;
+    l.B = a.B; l.H = a.H; l.W = a.W; l.C = a.C;
+    l.TH = pl.TH; l.TW = pl.TW; l.tiles_h = pl.tiles_h; l.tiles_w = pl.tiles_w; l.ntiles = pl.ntiles; l.dshift = pl.dshift; l.tshift = pl.tshift;
+    if (mte_allow_lds<K>(112 * 1024) != MTE_OK) return MTE_ERR_LAUNCH;
+    hipLaunchKernelGGL(K, dim3(pl.grid_x), dim3(pl.block), pl.lds, st, l);
     return mte_check_launch();
 }
 
-inline P3LArgs p3l_args(int B, int H, int W, int C) {
-    P3LArgs a{}; a.B = B; a.H = H; a.W = W; a.C = C;
-    const P3Tile t = p3_tile(C); a.TH = t.TH; a.TW = t.TW;
-    a.tiles_h = (H / 2 + t.TH - 1) / t.TH; a.tiles_w = (W / 2 + t.TW - 1) / t.TW; a.ntiles = a.tiles_h * a.tiles_w * B;
-    return a;
-}
+// Clear, pick the instance, launch.  The cases stand in the order in which the entry points used to name the instances: the order of the kernels in the
+// code object follows it, and the optimiser's output is not the same in every order.
+int launch_p3plan(const P3Plan& pl, P3Args a, hipStream_t st) {
+    using Op = P3Op; using F = P3Form;
+    if (pl.clear_dwb && mte_memset_async(a.dw3, 0, 112 * sizeof(float), st) != hipSuccess) return MTE_ERR_LAUNCH;
+    if (pl.rc != MTE_OK) return pl.rc;
+    a.total = pl.total;
+    switch (p3_key(pl)) {
+    case p3_key(Op::PackFwd, F::TapsK, 2, 4): return launch_tiled<pack3d_fwd_tr_kernel<2, 4>>(pl, a, st);
+    case p3_key(Op::PackFwd, F::Lds): return launch_tiled<pack3d_fwd_lds_kernel>(pl, a, st);
+    case p3_key(Op::PackFwd, F::Gather, 0, 4): return launch_gather<pack3d_fwd_kernel<bf16_t, 4>>(pl, a, st);
+    case p3_key(Op::PackFwd, F::Gather, 1, 4): return launch_gather<pack3d_fwd_kernel<float, 4>>(pl, a, st);
+    case p3_key(Op::PackFwd, F::Gather, 0, 8): return launch_gather<pack3d_fwd_kernel<bf16_t, 8>>(pl, a, st);
+    case p3_key(Op::PackFwd, F::Gather, 1, 8): return launch_gather<pack3d_fwd_kernel<float, 8>>(pl, a, st);
 
-int g_p3_lds = 2;                                   // development knob (mte_debug_set(1, v))
-int g_p3_mfma_threads = 512;
-int g_p3_mfma = 1;                                  // development knob (mte_debug_set(1, 200 + v)): conv3d weight gradients on the matrix cores
+    case p3_key(Op::PackBwdData, F::Mfma, 0): return launch_tiled<pack3d_bwd_data_mfma_kernel<false>>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Mfma, 1): return launch_tiled<pack3d_bwd_data_mfma_kernel<true>>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Lds): return launch_tiled<pack3d_bwd_data_lds_kernel>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Gather, 0, 4): return launch_gather<pack3d_bwd_data_kernel<bf16_t, 4>>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Gather, 1, 4): return launch_gather<pack3d_bwd_data_kernel<float, 4>>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Gather, 0, 8): return launch_gather<pack3d_bwd_data_kernel<bf16_t, 8>>(pl, a, st);
+    case p3_key(Op::PackBwdData, F::Gather, 1, 8): return launch_gather<pack3d_bwd_data_kernel<float, 8>>(pl, a, st);
+
+    case p3_key(Op::PackBwdWeight, F::WeightMfma): return launch_tiled<conv3d_bwd_weight_mfma_kernel<false>>(pl, a, st);
+    case p3_key(Op::PackBwdWeight, F::WeightLds): return launch_tiled<pack3d_bwd_weight_lds_kernel>(pl, a, st);
+    case p3_key(Op::PackBwdWeight, F::Gather, 0, 4): return launch_gather<pack3d_bwd_weight_kernel<bf16_t, 4>>(pl, a, st);
+    case p3_key(Op::PackBwdWeight, F::Gather, 1, 4): return launch_gather<pack3d_bwd_weight_kernel<float, 4>>(pl, a, st);
+    case p3_key(Op::PackBwdWeight, F::Gather, 0, 8): return launch_gather<pack3d_bwd_weight_kernel<bf16_t, 8>>(pl, a, st);
+    case p3_key(Op::PackBwdWeight, F::Gather, 1, 8): return launch_gather<pack3d_bwd_weight_kernel<float, 8>>(pl, a, st);
+
+    case p3_key(Op::UnpackFwd, F::TapsK, 32, 8, 1): return launch_tiled<unpack3d_fwd_tr_kernel<32, 8, 1>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 64, 4, 1): return launch_tiled<unpack3d_fwd_tr_kernel<64, 4, 1>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 128, 2, 1): return launch_tiled<unpack3d_fwd_tr_kernel<128, 2, 1>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 256, 1, 1): return launch_tiled<unpack3d_fwd_tr_kernel<256, 1, 1>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 32, 8, 2): return launch_tiled<unpack3d_fwd_tr_kernel<32, 8, 2>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 64, 4, 2): return launch_tiled<unpack3d_fwd_tr_kernel<64, 4, 2>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 128, 2, 2): return launch_tiled<unpack3d_fwd_tr_kernel<128, 2, 2>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 256, 1, 2): return launch_tiled<unpack3d_fwd_tr_kernel<256, 1, 2>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 32, 8, 4): return launch_tiled<unpack3d_fwd_tr_kernel<32, 8, 4>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 64, 4, 4): return launch_tiled<unpack3d_fwd_tr_kernel<64, 4, 4>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 128, 2, 4): return launch_tiled<unpack3d_fwd_tr_kernel<128, 2, 4>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::TapsK, 256, 1, 4): return launch_tiled<unpack3d_fwd_tr_kernel<256, 1, 4>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Mfma, 32, 0): return launch_tiled<unpack3d_fwd_mfma_kernel<32, false>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Mfma, 64, 0): return launch_tiled<unpack3d_fwd_mfma_kernel<64, false>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Mfma, 32, 1): return launch_tiled<unpack3d_fwd_mfma_kernel<32, true>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Mfma, 64, 1): return launch_tiled<unpack3d_fwd_mfma_kernel<64, true>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Gather, 0): return launch_gather<unpack3d_fwd_kernel<bf16_t>>(pl, a, st);
+    case p3_key(Op::UnpackFwd, F::Gather, 1): return launch_gather<unpack3d_fwd_kernel<float>>(pl, a, st);
+
+    case p3_key(Op::UnpackBwdData, F::Dma32, 4, 0): return launch_tiled<unpack3d_bwd_data_dma32_kernel<4, false>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Dma32, 4, 1): return launch_tiled<unpack3d_bwd_data_dma32_kernel<4, true>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Dma32, 2, 1): return launch_tiled<unpack3d_bwd_data_dma32_kernel<2, true>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Mfma, 32, 0): return launch_tiled<unpack3d_bwd_data_mfma_kernel<32, false>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Mfma, 64, 0): return launch_tiled<unpack3d_bwd_data_mfma_kernel<64, false>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Mfma, 32, 1): return launch_tiled<unpack3d_bwd_data_mfma_kernel<32, true>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Mfma, 64, 1): return launch_tiled<unpack3d_bwd_data_mfma_kernel<64, true>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Lds4): return launch_tiled<unpack3d_bwd_data_lds4_kernel>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Lds): return launch_tiled<unpack3d_bwd_data_lds_kernel>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Gather, 0): return launch_gather<unpack3d_bwd_data_kernel<bf16_t>>(pl, a, st);
+    case p3_key(Op::UnpackBwdData, F::Gather, 1): return launch_gather<unpack3d_bwd_data_kernel<float>>(pl, a, st);
+
+    case p3_key(Op::UnpackBwdWeight, F::WeightMfma): return launch_tiled<conv3d_bwd_weight_mfma_kernel<true>>(pl, a, st);
+    case p3_key(Op::UnpackBwdWeight, F::WeightLds): return launch_tiled<unpack3d_bwd_weight_lds_kernel>(pl, a, st);
+    case p3_key(Op::UnpackBwdWeight, F::Gather, 0): return launch_gather<unpack3d_bwd_weight_kernel<bf16_t>>(pl, a, st);
+    case p3_key(Op::UnpackBwdWeight, F::Gather, 1): return launch_gather<unpack3d_bwd_weight_kernel<float>>(pl, a, st);
+    }
+    return MTE_ERR_UNSUPPORTED;                         // (no plan names another instance)
+}
 
 }  // namespace
 
 #ifdef MTE_DEV
-extern "C" int mtei_set_pack3d_lds(int value) { if (value >= 3000) { g_p3_tr_passes = value - 3000 == 1 ? 1 : (value - 3000 == 2 ? 2 : 4); return MTE_OK; } if (value >= 2000) { g_p3_persist_wgs = value - 2000; return MTE_OK; } if (value >= 1000) { g_p3_mfma_threads = value - 1000; return MTE_OK; } if (value >= 300) { g_p3_mfma_data = value - 300; return MTE_OK; } if (value >= 200) { g_p3_mfma = value - 200; return MTE_OK; } if (value >= 100) { g_p3_small_tiles = value - 100; return MTE_OK; } g_p3_lds = value; return MTE_OK; }
+extern "C" int mtei_set_pack3d_lds(int value) { return p3_knob_set(g_pack3d_knobs, value); }
 #endif
 
 
@@ -1856,167 +1864,47 @@ extern "C" {
 int mte_pack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, void* out, long ldo,
                    int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !w3 || !b3 || !out || !p3_ok(C) || (H & 1) || (W & 1)) return MTE_ERR_ARG;
+    if (!x || !w3 || !b3 || !out) return MTE_ERR_ARG;
     P3Args a{}; a.x = x; a.ldx = ldx; a.dst = out; a.lddst = ldo; a.w3 = w3; a.b3 = b3; a.B = B; a.H = H; a.W = W; a.C = C;
-    a.total = (long)B * (H / 2) * (W / 2) * (C / 8);
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 64) && C % 32 == 0) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C; l.TH = 2; l.TW = 16;
-        l.tiles_h = (H / 2 + l.TH - 1) / l.TH; l.tiles_w = (W / 2 + l.TW - 1) / l.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
-        const long grid = (long)l.ntiles * (4 * C / 128);
-        if (grid < (1L << 30)) return launch_p3l<pack3d_fwd_tr_kernel<2, 4>>(l, (int)grid, stream, (size_t)4 * 18 * 448 + (size_t)8 * 1024);
-    }
-    if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
-        P3LArgs l = p3l_args(B, H, W, C); l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
-        return launch_p3l<pack3d_fwd_lds_kernel>(l, l.ntiles, stream);
-    }
-    if (C <= 256) { a.total *= 2; return launch_p3(dtype, pack3d_fwd_kernel<bf16_t, 4>, pack3d_fwd_kernel<float, 4>, a, a.total, stream); }
-    return launch_p3(dtype, pack3d_fwd_kernel<bf16_t, 8>, pack3d_fwd_kernel<float, 8>, a, a.total, stream);
+    return launch_p3plan(plan_p3({P3Op::PackFwd, dtype, B, H, W, C, ldx, ldo}, g_pack3d_knobs), a, stream);
 }
 int mte_pack3d_bwd_data(const void* dout, long ldo, const float* w3, void* dx, long lddx,
                         int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!dout || !w3 || !dx || !p3_ok(C)) return MTE_ERR_ARG;
+    if (!dout || !w3 || !dx) return MTE_ERR_ARG;
     P3Args a{}; a.o = dout; a.ldo = ldo; a.dst = dx; a.lddst = lddx; a.w3 = w3; a.B = B; a.H = H; a.W = W; a.C = C;
-    a.total = (long)B * (H / 2) * (W / 2) * (C / 8);
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 128) && C % 32 == 0 && ((long)B * (H / 2) * (W / 2) - 1) * ldo + 16L * C < (1L << 30)) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C; l.TH = 4; l.TW = 16;
-        l.tiles_h = (H / 2 + 3) / 4; l.tiles_w = (W / 2 + 15) / 16; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        const long grid = (long)l.ntiles * (4 * C / 128);
-        if (grid < (1L << 30))
-            return (g_p3_mfma_data & 16) ? launch_p3l<pack3d_bwd_data_mfma_kernel<false>>(l, (int)grid, stream, (size_t)7 * 20 * 256)
-                                         : launch_p3l<pack3d_bwd_data_mfma_kernel<true>>(l, (int)grid, stream, (size_t)7 * 20 * 256);
-    }
-    if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
-        P3LArgs l = p3l_args(B, H, W, C); l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l<pack3d_bwd_data_lds_kernel>(l, l.ntiles, stream);
-    }
-    if (C <= 256) { a.total *= 2; return launch_p3(dtype, pack3d_bwd_data_kernel<bf16_t, 4>, pack3d_bwd_data_kernel<float, 4>, a, a.total, stream); }
-    return launch_p3(dtype, pack3d_bwd_data_kernel<bf16_t, 8>, pack3d_bwd_data_kernel<float, 8>, a, a.total, stream);
+    return launch_p3plan(plan_p3({P3Op::PackBwdData, dtype, B, H, W, C, lddx, ldo}, g_pack3d_knobs), a, stream);
 }
 // dwb[112] (fp32, zeroed here): [0..107] = dw3, [108..111] = db3
 int mte_pack3d_bwd_weight(const void* x, long ldx, const void* dout, long ldo, float* dwb,
                           int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !dout || !dwb || !p3_ok(C)) return MTE_ERR_ARG;
-    if (mte_memset_async(dwb, 0, 112 * sizeof(float), stream) != hipSuccess) return MTE_ERR_LAUNCH;
+    if (!x || !dout || !dwb) return MTE_ERR_ARG;
     P3Args a{}; a.x = x; a.ldx = ldx; a.o = dout; a.ldo = ldo; a.dw3 = dwb; a.B = B; a.H = H; a.W = W; a.C = C;
-    a.total = (long)B * (H / 2) * (W / 2) * (C / 8);
-    if (dtype == MTE_DT_BF16 && g_p3_lds && C % 8 == 0 && C <= 512) {
-        P3LArgs l = p3l_args(B, H, W, C); l.x = (const bf16_t*)x; l.ldx = ldx; l.o = (const bf16_t*)dout; l.ldo = ldo; l.dwb = dwb;
-        { const int dpairs = 4 * C / 16; l.dshift = (dpairs & (dpairs - 1)) == 0 ? __builtin_ctz(dpairs) : -1; l.tshift = __builtin_ctz(l.TW); }
-        if (g_p3_mfma) return launch_p3l<conv3d_bwd_weight_mfma_kernel<false>>(l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, p3_lds_bytes(C) + 16, g_p3_mfma_threads);
-        return launch_p3l<pack3d_bwd_weight_lds_kernel>(l, l.ntiles < 512 ? l.ntiles : 512, stream);
-    }
-    if (C <= 256) a.total *= 2;
-    long threads = a.total < 256L * 1024 ? a.total : 256L * 1024;
-    if (C <= 256) return launch_p3(dtype, pack3d_bwd_weight_kernel<bf16_t, 4>, pack3d_bwd_weight_kernel<float, 4>, a, threads, stream, 3);
-    return launch_p3(dtype, pack3d_bwd_weight_kernel<bf16_t, 8>, pack3d_bwd_weight_kernel<float, 8>, a, threads, stream, 3);
+    return launch_p3plan(plan_p3({P3Op::PackBwdWeight, dtype, B, H, W, C, ldx, ldo}, g_pack3d_knobs), a, stream);
 }
 
 // out[B,2H,2W,C] = pixel_shuffle(conv3d(x[B,H,W,C]))                   (UnpackLayerConv3d after its Conv2D)
 int mte_unpack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, void* out, long ldo,
                      int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !w3 || !b3 || !out || !p3_ok(C)) return MTE_ERR_ARG;
+    if (!x || !w3 || !b3 || !out) return MTE_ERR_ARG;
     P3Args a{}; a.x = x; a.ldx = ldx; a.dst = out; a.lddst = ldo; a.w3 = w3; a.b3 = b3; a.B = B; a.H = H; a.W = W; a.C = C;
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 32) && (C == 32 || C == 64 || C == 128 || C == 256)) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
-        l.TH = 256 / C; l.TW = 16;
-        l.tiles_h = (H + l.TH - 1) / l.TH; l.tiles_w = (W + l.TW - 1) / l.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
-        const int rs = (C * 2) % 128 == 64 ? C * 2 : C * 2 + 64;
-        const int nh = g_p3_tr_passes;
-        const size_t lds = (size_t)(l.TH + 2) * 18 * rs + (size_t)l.TH * 16 * 8 * C / nh;
-        if (nh == 1) {
-            if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 1>>(l, l.ntiles, stream, lds);
-            if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 1>>(l, l.ntiles, stream, lds);
-            if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 1>>(l, l.ntiles, stream, lds);
-            return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 1>>(l, l.ntiles, stream, lds);
-        }
-        if (nh == 2) {
-            if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 2>>(l, l.ntiles, stream, lds);
-            if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 2>>(l, l.ntiles, stream, lds);
-            if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 2>>(l, l.ntiles, stream, lds);
-            return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 2>>(l, l.ntiles, stream, lds);
-        }
-        if (C == 32) return launch_p3l<unpack3d_fwd_tr_kernel<32, 8, 4>>(l, l.ntiles, stream, lds);
-        if (C == 64) return launch_p3l<unpack3d_fwd_tr_kernel<64, 4, 4>>(l, l.ntiles, stream, lds);
-        if (C == 128) return launch_p3l<unpack3d_fwd_tr_kernel<128, 2, 4>>(l, l.ntiles, stream, lds);
-        return launch_p3l<unpack3d_fwd_tr_kernel<256, 1, 4>>(l, l.ntiles, stream, lds);
-    }
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 8) && (C == 32 || C == 64) && ((long)B * H * W - 1) * ldx + C < (1L << 30)) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
-        l.TH = C == 32 ? 8 : 4; l.TW = 16;
-        l.tiles_h = (H + l.TH - 1) / l.TH; l.tiles_w = (W + l.TW - 1) / l.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.x = (const bf16_t*)x; l.ldx = ldx; l.dst = (bf16_t*)out; l.lddst = ldo; l.w3 = w3; l.b3 = b3;
-        const size_t lds = (size_t)2 * (((l.TH + 2) * 18 + 15) / 16) * (C / 8 + 2) * 256;      // two tile buffers
-        const int grid = l.ntiles < g_p3_persist_wgs ? l.ntiles : g_p3_persist_wgs;            // persistent workgroups (a multiple of 8: tile % 8 = XCD)
-        if (g_p3_mfma_data & 16) {
-            if (C == 32) return launch_p3l<unpack3d_fwd_mfma_kernel<32, false>>(l, grid, stream, lds);
-            return launch_p3l<unpack3d_fwd_mfma_kernel<64, false>>(l, grid, stream, lds);
-        }
-        if (C == 32) return launch_p3l<unpack3d_fwd_mfma_kernel<32, true>>(l, grid, stream, lds);
-        return launch_p3l<unpack3d_fwd_mfma_kernel<64, true>>(l, grid, stream, lds);
-    }
-    a.total = (long)B * H * W * (C / 8);
-    return launch_p3(dtype, unpack3d_fwd_kernel<bf16_t>, unpack3d_fwd_kernel<float>, a, a.total, stream);
+    return launch_p3plan(plan_p3({P3Op::UnpackFwd, dtype, B, H, W, C, ldx, ldo}, g_pack3d_knobs), a, stream);
 }
 int mte_unpack3d_bwd_data(const void* dout, long ldo, const float* w3, void* dx, long lddx,
                           int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!dout || !w3 || !dx || !p3_ok(C)) return MTE_ERR_ARG;
+    if (!dout || !w3 || !dx) return MTE_ERR_ARG;
     P3Args a{}; a.o = dout; a.ldo = ldo; a.dst = dx; a.lddst = lddx; a.w3 = w3; a.B = B; a.H = H; a.W = W; a.C = C;
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && (g_p3_mfma_data & 1) && (C == 32 || C == 64)) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
-        l.TH = C == 32 ? 8 : 4; l.TW = 16;
-        l.tiles_h = (H + l.TH - 1) / l.TH; l.tiles_w = (W + l.TW - 1) / l.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        const size_t lds = (size_t)4 * (l.TH + 2) * (l.TW + 2) * (C + 16) * 2;
-        if (C == 32 && (g_p3_mfma_data & 2) && ((long)B * 4 * H * W - 1) * ldo + 32 < (1L << 30)) {
-            if (g_p3_mfma_data & 16) return launch_p3l<unpack3d_bwd_data_dma32_kernel<4, false>>(l, l.ntiles, stream, (size_t)180 * 256, 256);
-            if (g_p3_mfma_data & 4) return launch_p3l<unpack3d_bwd_data_dma32_kernel<4, true>>(l, l.ntiles, stream, (size_t)180 * 256, 256);
-            return launch_p3l<unpack3d_bwd_data_dma32_kernel<2, true>>(l, l.ntiles, stream, (size_t)180 * 256, 128);
-        }
-        if (g_p3_mfma_data & 16) {
-            if (C == 32) return launch_p3l<unpack3d_bwd_data_mfma_kernel<32, false>>(l, l.ntiles, stream, lds);
-            return launch_p3l<unpack3d_bwd_data_mfma_kernel<64, false>>(l, l.ntiles, stream, lds);
-        }
-        if (C == 32) return launch_p3l<unpack3d_bwd_data_mfma_kernel<32, true>>(l, l.ntiles, stream, lds);
-        return launch_p3l<unpack3d_bwd_data_mfma_kernel<64, true>>(l, l.ntiles, stream, lds);
-    }
-    if (dtype == MTE_DT_BF16 && g_p3_lds >= 2 && C % 32 == 0 && C <= 128) {
-        P3LArgs l{}; l.B = B; l.H = H; l.W = W; l.C = C;
-        const P3Tile t = up4_tile(C); l.TH = t.TH; l.TW = t.TW;
-        l.tiles_h = (H + t.TH - 1) / t.TH; l.tiles_w = (W + t.TW - 1) / t.TW; l.ntiles = l.tiles_h * l.tiles_w * B;
-        l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l<unpack3d_bwd_data_lds4_kernel>(l, l.ntiles, stream, up4_lds_bytes(C));
-    }
-    if (dtype == MTE_DT_BF16 && g_p3_lds && C % 32 == 0 && C <= 512) {
-        P3LArgs l = upl_args(B, H, W, C); l.o = (const bf16_t*)dout; l.ldo = ldo; l.dst = (bf16_t*)dx; l.lddst = lddx; l.w3 = w3;
-        return launch_p3l<unpack3d_bwd_data_lds_kernel>(l, l.ntiles, stream, up_lds_bytes(C));
-    }
-    a.total = (long)B * H * W * (C / 8);
-    return launch_p3(dtype, unpack3d_bwd_data_kernel<bf16_t>, unpack3d_bwd_data_kernel<float>, a, a.total, stream);
+    return launch_p3plan(plan_p3({P3Op::UnpackBwdData, dtype, B, H, W, C, lddx, ldo}, g_pack3d_knobs), a, stream);
 }
 int mte_unpack3d_bwd_weight(const void* x, long ldx, const void* dout, long ldo, float* dwb,
                             int B, int H, int W, int C, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !dout || !dwb || !p3_ok(C)) return MTE_ERR_ARG;
-    if (mte_memset_async(dwb, 0, 112 * sizeof(float), stream) != hipSuccess) return MTE_ERR_LAUNCH;
+    if (!x || !dout || !dwb) return MTE_ERR_ARG;
     P3Args a{}; a.x = x; a.ldx = ldx; a.o = dout; a.ldo = ldo; a.dw3 = dwb; a.B = B; a.H = H; a.W = W; a.C = C;
-    if (dtype == MTE_DT_BF16 && g_p3_lds && C % 32 == 0 && C <= 512) {
-        P3LArgs l = upl_args(B, H, W, C, g_p3_small_tiles != 0); l.x = (const bf16_t*)x; l.ldx = ldx; l.o = (const bf16_t*)dout; l.ldo = ldo; l.dwb = dwb;
-        const size_t lds = (size_t)(l.TH + 2) * (l.TW + 2) * LDP(C) * 2;
-        const int cap = g_p3_small_tiles ? 1024 : 512;
-        { const int dpairs = C / 16; l.dshift = (dpairs & (dpairs - 1)) == 0 ? __builtin_ctz(dpairs) : -1; l.tshift = __builtin_ctz(l.TW); }
-        if (g_p3_mfma) return launch_p3l<conv3d_bwd_weight_mfma_kernel<true>>(l, l.ntiles < MTE_P3W_WGS ? l.ntiles : MTE_P3W_WGS, stream, lds + 16, g_p3_mfma_threads);
-        return launch_p3l<unpack3d_bwd_weight_lds_kernel>(l, l.ntiles < cap ? l.ntiles : cap, stream, lds);
-    }
-    a.total = (long)B * H * W * (C / 8);
-    long threads = a.total < 256L * 2048 ? a.total : 256L * 2048;
-    return launch_p3(dtype, unpack3d_bwd_weight_kernel<bf16_t>, unpack3d_bwd_weight_kernel<float>, a, threads, stream, 3);
+    return launch_p3plan(plan_p3({P3Op::UnpackBwdWeight, dtype, B, H, W, C, ldx, ldo}, g_pack3d_knobs), a, stream);
 }
 
 }  // extern "C"

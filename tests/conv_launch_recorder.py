@@ -4,10 +4,11 @@ conv_igemm.hip and conv_igemm8.hip are compiled for the host alone (hipcc --cuda
 into a line of text, and linked with tests/conv_launch_driver.cpp, which calls the three C entry points.  tests/conv_launch_table.json holds one line per case:
 the case (the driver's input line) and what was launched.  tests/test_conv_launch_table_cpu.py requires the working tree to reproduce every line.
 --gn: the same for norm_act.hip with tests/gn_launch_driver.cpp (four entry points, two queries, the clears) and tests/gn_launch_table.json
-(tests/test_gn_launch_table_cpu.py).
+(tests/test_gn_launch_table_cpu.py).  --p3: the same for pack3d.hip with tests/p3_launch_driver.cpp (the six conv3d pack / unpack entry points) and
+tests/p3_launch_table.json (tests/test_p3_launch_table_cpu.py).
 
-    python tests/conv_launch_recorder.py [--gn] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
-    python tests/conv_launch_recorder.py [--gn] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+    python tests/conv_launch_recorder.py [--gn | --p3] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py [--gn | --p3] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
 """
 import argparse
 import json
@@ -21,19 +22,26 @@ TESTS = os.path.join(ROOT, "tests")
 CSRC = os.path.join(ROOT, "mindtheedge_amd", "csrc")
 TABLE = os.path.join(TESTS, "conv_launch_table.json")
 GN_TABLE = os.path.join(TESTS, "gn_launch_table.json")
+P3_TABLE = os.path.join(TESTS, "p3_launch_table.json")
 HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
 BF16, F32 = 0, 1
 SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
 
 
-def build(out_dir, dev, csrc=CSRC, extra=(), gn=False):
-    """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it)"""
-    exe = os.path.join(out_dir, ("gn_" if gn else "") + ("recorder_dev" if dev else "recorder"))
+def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False):
+    """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it;
+    p3: the conv3d pack / unpack driver and pack3d.hip)"""
+    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "") + ("recorder_dev" if dev else "recorder"))
     cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
     cmd += ["-DMTE_DEV"] if dev else []
     cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip")]
-    cmd += [os.path.join(csrc, "norm_act.hip"), os.path.join(TESTS, "gn_launch_driver.cpp")] if gn else [os.path.join(TESTS, "conv_launch_driver.cpp")]
+    if gn:
+        cmd += [os.path.join(csrc, "norm_act.hip"), os.path.join(TESTS, "gn_launch_driver.cpp")]
+    elif p3:
+        cmd += [os.path.join(csrc, "pack3d.hip"), os.path.join(TESTS, "p3_launch_driver.cpp")]
+    else:
+        cmd += [os.path.join(TESTS, "conv_launch_driver.cpp")]
     cmd += ["-o", exe]
     subprocess.run(cmd, check=True, capture_output=True, text=True)
     return exe
@@ -305,11 +313,170 @@ def gn_cases():
     seen = set()
     return [c for c in out if not (c in seen or seen.add(c))]
 
+# ---- conv3d pack / unpack (--p3).  (C, B, H, W) of tests/test_gpu_pack3d_variants.py, H and W of the un-packed side
+P3_OPS = ("pack_fwd", "pack_bwd_data", "pack_bwd_weight", "unpack_fwd", "unpack_bwd_data", "unpack_bwd_weight")
+P3_T_PACK = [(32, 2, 16, 32), (32, 1, 20, 36), (64, 1, 12, 40), (128, 1, 8, 16), (256, 1, 4, 16), (512, 1, 4, 8), (16, 2, 8, 12)]
+P3_T_UNPACK = [(32, 2, 12, 20), (32, 1, 17, 33), (64, 1, 9, 40), (128, 1, 8, 16), (256, 1, 5, 16), (512, 1, 4, 8)]
+P3_T_UNPACK_BWD = [(32, 2, 16, 32), (32, 1, 17, 33), (32, 3, 8, 16), (32, 1, 1, 1), (32, 1, 9, 47), (64, 1, 12, 48), (64, 2, 5, 19), (64, 1, 4, 16), (32, 2, 96, 160)]
+P3_T_UNPACK_FWD = P3_T_UNPACK_BWD + [(128, 1, 7, 21), (128, 2, 8, 16), (256, 1, 5, 16), (256, 2, 3, 33)]
+P3_T_PACK_FWD = [(32, 2, 16, 32), (32, 1, 6, 70), (64, 1, 12, 40), (64, 2, 10, 6), (128, 1, 8, 36), (256, 1, 4, 34), (512, 1, 4, 8), (64, 16, 6, 64)]
+P3_T_PACK_BWD = [(32, 2, 16, 32), (32, 1, 18, 34), (32, 3, 8, 64), (32, 1, 2, 2), (32, 1, 10, 94), (64, 1, 12, 48), (64, 2, 10, 38), (128, 1, 8, 36), (256, 1, 4, 34),
+                 (512, 1, 4, 8), (32, 2, 96, 160), (64, 16, 6, 64)]
+# tools/conv3d_bench.py (B = 8), p3_wgrad_bench.py (B = 8: (kind, C, H, W)) and loss_conv3d_race_stress.py
+P3_TOOL_BENCH = [("unpack_bwd_data", 32, 192, 640), ("unpack_bwd_data", 64, 96, 320), ("unpack_bwd_data", 128, 48, 160), ("unpack_fwd", 32, 192, 640),
+                 ("unpack_fwd", 64, 96, 320), ("unpack_fwd", 128, 48, 160), ("unpack_fwd", 256, 24, 80), ("pack_bwd_data", 32, 192, 640), ("pack_bwd_data", 64, 96, 320),
+                 ("pack_bwd_data", 128, 48, 160), ("pack_bwd_data", 256, 48, 160), ("pack_bwd_data", 512, 24, 80), ("pack_fwd", 256, 48, 160), ("pack_fwd", 512, 24, 80)]
+P3_TOOL_WGRAD = [("pack", 64, 384, 1280), ("pack", 64, 192, 640), ("pack", 128, 96, 320), ("pack", 256, 48, 160), ("pack", 512, 24, 80), ("unpack", 512, 12, 40),
+                 ("unpack", 256, 24, 80), ("unpack", 128, 48, 160), ("unpack", 64, 96, 320), ("unpack", 64, 192, 640)]
+P3_TOOL_RACE = [(32, 8, 192, 640), (64, 8, 96, 320), (32, 2, 50, 70)]
+P3W_WGS = 512                       # MTE_P3W_WGS (csrc/p3_plan.hpp)
 
-def record(csrc=CSRC, dev=True, extra=(), gn=False):
+
+def p3_training_shapes():
+    """(op, B, H, W, C, ldx, ldo) of every conv3d pack / unpack call of the T8 training step, bench.py's size (PackNetSAN01 at 8 x 384 x 1280, n1 .. n5 = 32, 64,
+    128, 256, 512).  pack1 .. pack3 are folded into their convolution (kernels.PackFoldedConvGnEluFn) and run the conv3d kernels on the exact border bands only,
+    top + bottom and left + right as one batch of 16; pack4 and pack5 run them whole.  unpack5 .. unpack1 write their result into the decoder's concat buffers
+    (pixel stride: their own channels + the skip's), and their gradient arrives as a slice of such a buffer or as a tensor of its own."""
+    out = []
+    for C, H, W, k in ((32, 384, 1280, 5), (64, 192, 640, 3), (128, 96, 320, 3)):
+        hb = 2 * (k // 2) + 1
+        for h, w in ((2 * hb, W), (H, 2 * hb)):
+            out += [(op, 16, h, w, C, C, 16 * C) for op in P3_OPS[:3]]
+    for C, H, W in ((256, 48, 160), (512, 24, 80)):
+        out += [(op, 8, H, W, C, C, 16 * C) for op in P3_OPS[:3]]
+    for C, H, W, skip in ((512, 12, 40, 256), (256, 24, 80, 128), (128, 48, 160, 64), (64, 96, 320, 32), (32, 192, 640, 32)):
+        for ldo in (C + skip, C):
+            out += [(op, 8, H, W, C, C, ldo) for op in P3_OPS[3:]]
+    return out
+
+
+def p3_case(op, dtype, B, H, W, C, ldx=None, ldo=None, knobs=None):
+    """ldx, ldo: None = the dense tensors' (C, and 16 C for the pack layers' feature side); knobs: values of mte_debug_set(1, .)"""
+    return "%s %d %d %d %d %d %d %d %s" % (op, dtype, B, H, W, C, C if ldx is None else ldx, (16 * C if op.startswith("pack") else C) if ldo is None else ldo,
+                                           ",".join("1=%d" % v for v in knobs) if knobs else "-")
+
+
+def p3_cases():
+    out = []
+
+    def add(*a, **kw):
+        c = p3_case(*a, **kw)
+        if c not in out:
+            out.append(c)
+
+    for op, B, H, W, C, ldx, ldo in p3_training_shapes():
+        for dtype in (BF16, F32):
+            add(op, dtype, B, H, W, C, ldx, ldo)
+    for op in P3_OPS:                                                      # an element type the library does not have
+        add(op, 2, 8, 48, 160, 256)
+
+    # ---- tests/test_gpu_pack3d_variants.py
+    for C, B, H, W in P3_T_PACK:
+        for lds in (1, 0):
+            for op in P3_OPS[:3]:
+                add(op, BF16, B, H, W, C, knobs=[lds])
+    for C, B, H, W in P3_T_UNPACK:
+        for lds in (0, 1, 2):
+            for op in P3_OPS[3:]:
+                add(op, BF16, B, H, W, C, knobs=[lds])
+    for C, B, H, W in P3_T_UNPACK_BWD:
+        for knob in (300, 301, 303, 307):
+            add("unpack_bwd_data", BF16, B, H, W, C, knobs=[knob])
+    for C, B, H, W in P3_T_UNPACK_FWD:
+        for knob in (307, 539) + ((315,) if C <= 64 else ()):
+            add("unpack_fwd", BF16, B, H, W, C, knobs=[knob, 2000 + 1024])
+        if C <= 64:
+            for wgs in (8, 24):
+                add("unpack_fwd", BF16, B, H, W, C, knobs=[315, 2000 + wgs])
+    for C, B, H, W in P3_T_PACK_FWD:
+        for knob in (539, 347):
+            add("pack_fwd", BF16, B, H, W, C, knobs=[knob])
+    for C, B, H, W in P3_T_PACK_BWD:
+        for knob in (411, 539, 555):
+            add("pack_bwd_data", BF16, B, H, W, C, knobs=[knob])
+
+    # ---- tools/conv3d_bench.py (its default variants, those its README row names, the output passes), p3_wgrad_bench.py, loss_conv3d_race_stress.py
+    seen_ops = set()
+    for op, C, H, W in P3_TOOL_BENCH:
+        for knob in (300, 411, 539) + ((315, 331, 347) if op not in seen_ops else ()):       # (the other variants on the first shape of each op)
+            add(op, BF16, 8, H, W, C, knobs=[knob])
+        seen_ops.add(op)
+        if op == "unpack_fwd":
+            for passes in (1, 2, 4):
+                add(op, BF16, 8, H, W, C, knobs=[539, 3000 + passes])
+    for kind, C, H, W in P3_TOOL_WGRAD:
+        for mfma, small in ((0, 1), (1, 0), (1, 1)):
+            add(kind + "_bwd_weight", BF16, 8, H, W, C, knobs=[200 + mfma, 100 + small])
+    for C, B, H, W in P3_TOOL_RACE:
+        for op in ("unpack_fwd", "unpack_bwd_data"):
+            add(op, BF16, B, H, W, C)
+
+    # ---- thresholds, one group at a time
+    for C in (8, 16, 24, 32, 64, 128, 256, 512, 1024):                     # every C the library takes, one between and one above (refused)
+        for op in P3_OPS:
+            for dtype in (BF16, F32):
+                add(op, dtype, 2, 24, 40, C)
+            for knobs in ([0], [1]) + (([300], [555]) if op.endswith("_data") else ([300], [331]) if op.endswith("_fwd") else ()):
+                add(op, BF16, 2, 24, 40, C, knobs=knobs)
+    for H, W in ((23, 40), (24, 39), (1, 1), (2, 2)):                      # odd H or W: refused by the pack forward alone
+        for op in P3_OPS:
+            add(op, BF16, 2, H, W, 64)
+            add(op, F32, 2, H, W, 64)
+    # tile counts on both sides of a whole tile: every tile is 1 .. 16 rows of 2 .. 32 pixels, so a 32 x 64 volume is whole tiles of every shape and 33 x 65 one
+    # row and one column more (pack: the packed side, half of H and W).  Tiles: p3_tile small and large, 2 x 16 (taps in K), 4 x 16 (banded) for pack; up_tile
+    # whole and halved, up4_tile, 256 / C x 16 (taps in K), 8 or 4 x 16 (banded) for unpack
+    per_op = {"pack_fwd": ([347], [100]), "pack_bwd_data": ([411], [100]), "pack_bwd_weight": ([100], [100, 200], [200]),          # (what steers each op's tiles)
+              "unpack_fwd": ([315], [300]), "unpack_bwd_data": ([301], [300], [1]), "unpack_bwd_weight": ([100], [100, 200], [200])}
+    for C in (32, 64, 128, 256, 512):
+        for d in (0, 1):
+            for op in P3_OPS:
+                for knobs in (None,) + per_op[op]:
+                    if op.startswith("pack"):
+                        add(op, BF16, 3, 2 * (32 + d), 2 * (64 + d), C, knobs=knobs)
+                    else:
+                        add(op, BF16, 3, 32 + d, 64 + d, C, knobs=knobs)
+    # ntiles on both sides of every workgroup cap: the weight gradients' 512 (LDS kernels; unpack: 1024 with the small tiles), MTE_P3W_WGS, persist_wgs
+    for cap in sorted({512, 1024, P3W_WGS}):
+        for n in (cap - 1, cap, cap + 1):
+            for knobs in (None, [200], [200, 100], [100]):
+                add("pack_bwd_weight", BF16, n, 8, 32, 32, knobs=knobs)                      # (one 4 x 16 or 8 x 16 tile per sample)
+                add("unpack_bwd_weight", BF16, n, 8, 32, 32, knobs=knobs)                   # (one 8 x 32 or 16 x 32 tile per sample)
+    for wgs in (8, 24, 1024):
+        for n in (wgs - 1, wgs, wgs + 1):
+            add("unpack_fwd", BF16, n, 8, 16, 32, knobs=[315, 2000 + wgs])                   # (one 8 x 16 tile per sample)
+    for threads in (256, 512, 1024):                                       # threads of the matrix-core weight gradient
+        add("pack_bwd_weight", BF16, 8, 48, 160, 256, knobs=[1000 + threads])
+        add("unpack_bwd_weight", BF16, 8, 24, 80, 256, knobs=[1000 + threads])
+    # the gather weight gradients' thread caps: 256 * 1024 (pack) and 256 * 2048 (unpack) threads with work
+    for W in (2 * 4096 - 2, 2 * 4096, 2 * 4096 + 2):                       # 64 channels: 16 threads per packed pixel
+        add("pack_bwd_weight", F32, 4, 2, W, 64)
+    for W in (8192 - 1, 8192, 8192 + 1):                                   # 512 channels: 64 threads per pixel
+        add("unpack_bwd_weight", F32, 1, 1, W, 512)
+    # ldx / ldo one step inside and one step outside each 1 << 30 element bound
+    lim = 1 << 30
+    for B, H, W, C in ((8, 48, 160, 256), (8, 48, 160, 32)):                                  # pack backward data: (pixels - 1) * ldo + 16 C < lim
+        edge = (lim - 1 - 16 * C) // (B * (H // 2) * (W // 2) - 1)
+        for ldo in (edge, edge + 1):
+            add("pack_bwd_data", BF16, B, H, W, C, ldo=ldo)
+    for C in (32, 64):                                                     # banded unpack forward: (pixels - 1) * ldx + C < lim
+        edge = (lim - 1 - C) // (8 * 96 * 320 - 1)
+        for ldx in (edge, edge + 1):
+            add("unpack_fwd", BF16, 8, 96, 320, C, ldx=ldx, knobs=[315])
+    edge = (lim - 1 - 32) // (8 * 4 * 192 * 640 - 1)                        # LDS-DMA unpack backward data: (4 pixels - 1) * ldo + 32 < lim
+    for ldo in (edge, edge + 1):
+        for knobs in (None, [303], [331]):
+            add("unpack_bwd_data", BF16, 8, 192, 640, 32, ldo=ldo, knobs=knobs)
+    # the grid < 1 << 30 test of the two depth-slab forms: tiles x (4 C / 128) slabs, at C = 512 (16 slabs) with one packed pixel per sample
+    for B in (lim // 16 - 1, lim // 16):
+        add("pack_fwd", BF16, B, 2, 2, 512)
+        add("pack_bwd_data", BF16, B, 2, 2, 512, ldo=8)
+    return out
+
+
+def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False):
     with tempfile.TemporaryDirectory() as tmp:
-        cs = gn_cases() if gn else cases()
-        return run(build(tmp, dev, csrc, extra, gn), cs if dev else [c for c in cs if c.endswith(" -")])
+        cs = gn_cases() if gn else p3_cases() if p3 else cases()
+        return run(build(tmp, dev, csrc, extra, gn, p3), cs if dev else [c for c in cs if c.endswith(" -")])
 
 
 def load_table(path=TABLE):
@@ -325,10 +492,11 @@ if __name__ == "__main__":
     ap.add_argument("--write", action="store_true")
     ap.add_argument("--product", action="store_true", help="the build without -DMTE_DEV: the cases that set no knob")
     ap.add_argument("--gn", action="store_true", help="GroupNorm (norm_act.hip, tests/gn_launch_table.json)")
+    ap.add_argument("--p3", action="store_true", help="conv3d pack / unpack (pack3d.hip, tests/p3_launch_table.json)")
     a = ap.parse_args()
-    lines = record(a.csrc, dev=not a.product, gn=a.gn)
+    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3)
     for ln in lines:
         json.loads(ln)
-    with open((GN_TABLE if a.gn else TABLE) if a.write else a.out, "w") as f:
+    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else TABLE) if a.write else a.out, "w") as f:
         f.write("[\n" + ",\n".join(lines) + "\n]\n")
     print("%d cases" % len(lines))

@@ -1,7 +1,7 @@
 // Launch recorder for the host code that chooses kernels (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip /
-// norm_act.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
+// norm_act.hip / pack3d.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
 // call reaches the HIP runtime: every launch is appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the
-// large-LDS grant the kernel holds at that moment, and for a ConvArgs or GnArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
+// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args or P3LArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
 // kernels of mte_memset_async in common.hpp) is a line of its own: which buffer and how many bytes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -30,10 +30,15 @@ template <auto K> std::string kernel_name() {
     std::string s = d ? d : typeid(Tag<K>).name();
     free(d);
     for (size_t at; (at = s.find("(anonymous namespace)::")) != std::string::npos;) s.erase(at, 23);
-    size_t from = s.find("&(");                                             // (a kernel that is no template carries no return type)
-    from = from == std::string::npos ? 0 : from + 2;
-    if (s.compare(from, 5, "void ") == 0) from += 5;
-    s = s.substr(from, s.find('(', from) - from);
+    size_t from = s.find("&(");
+    if (from == std::string::npos) {                                        // a kernel that is no template: "mte_rec::Tag<&pack3d_fwd_lds_kernel>"
+        from = s.find('&');
+        if (from != std::string::npos) s = s.substr(from + 1, s.rfind('>') - from - 1);
+    } else {
+        from += 2;
+        if (s.compare(from, 5, "void ") == 0) from += 5;
+        s = s.substr(from, s.find('(', from) - from);
+    }
     for (size_t at; (at = s.find("unsigned short")) != std::string::npos;) s.replace(at, 14, "bf16");
     return s;
 }
@@ -42,6 +47,10 @@ inline void field(const char* name, long v, long dflt) { if (v != dflt) log() +=
 
 template <typename A, typename = void> struct is_gn_args : std::false_type {};
 template <typename A> struct is_gn_args<A, std::void_t<decltype(A::cps_shift), decltype(A::blocks_per_sample), decltype(A::ppl)>> : std::true_type {};
+template <typename A, typename = void> struct is_p3_args : std::false_type {};       // P3Args: the conv3d gather kernels
+template <typename A> struct is_p3_args<A, std::void_t<decltype(A::dw3), decltype(A::db3), decltype(A::total)>> : std::true_type {};
+template <typename A, typename = void> struct is_p3l_args : std::false_type {};      // P3LArgs: every other conv3d kernel
+template <typename A> struct is_p3l_args<A, std::void_t<decltype(A::dwb), decltype(A::tiles_h), decltype(A::tshift)>> : std::true_type {};
 
 // (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other fields 0, a pointer null)
 template <typename A> void arg_fields(const A& a) {
@@ -52,6 +61,15 @@ template <typename A> void arg_fields(const A& a) {
         field("ppl", a.ppl, 0); field("b0", a.b0, 0); field("nb", a.nb, 0);
         const std::string with = std::string(a.y2 ? " y2" : "") + (a.scale2 ? " scale2" : "") + (a.d2 ? " d2" : "") + (a.dbias ? " dbias" : "");
         if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";      // the optional pointers that are not null
+    } else if constexpr (is_p3_args<A>::value) {
+        field("total", a.total, 0); field("ldx", a.ldx, 0); field("ldo", a.ldo, 0); field("lddst", a.lddst, 0);
+        const std::string with = std::string(a.x ? " x" : "") + (a.o ? " o" : "") + (a.dst ? " dst" : "") + (a.w3 ? " w3" : "") + (a.b3 ? " b3" : "") + (a.dw3 ? " dw3" : "") + (a.db3 ? " db3" : "");
+        if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";
+    } else if constexpr (is_p3l_args<A>::value) {
+        field("TH", a.TH, 0); field("TW", a.TW, 0); field("tiles_h", a.tiles_h, 0); field("tiles_w", a.tiles_w, 0); field("ntiles", a.ntiles, 0);
+        field("dshift", a.dshift, 0); field("tshift", a.tshift, 0); field("ldx", a.ldx, 0); field("ldo", a.ldo, 0); field("lddst", a.lddst, 0);
+        const std::string with = std::string(a.x ? " x" : "") + (a.o ? " o" : "") + (a.dst ? " dst" : "") + (a.w3 ? " w3" : "") + (a.b3 ? " b3" : "") + (a.dwb ? " dwb" : "");
+        if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";
     }
 }
 

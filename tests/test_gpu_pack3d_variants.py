@@ -6,7 +6,7 @@ import torch
 from conftest import rel_err, kernel_variant
 
 pytestmark = pytest.mark.gpu
-PRODUCT = 539        # development knob 1 = 300 + g_p3_mfma_data of the product build (csrc/pack3d.hip)
+PRODUCT = 539        # development knob 1 = 300 + P3_MFMA_DATA_PRODUCT (csrc/p3_plan.hpp, where the P3_* bits of the values below are named)
 
 
 def _run(C, B, H, W, lds):
@@ -62,8 +62,7 @@ def test_lds_unpack3d_backward_matches_gather(C, B, H, W):
 
 
 def _unpack_bwd_data(C, B, H, W, knob, seed):
-    """dx of the unpack layer's conv3d for one kernel variant (development knob 1: 300 = fp32-VALU stencil, 301 = matrix cores with interleaved
-    planes, 303 / 307 = + raw records by LDS-DMA for C = 32 with 2 / 4 waves; + 8 = forward as banded GEMM, + 32 = unpack forward with the spatial taps in K, + 64 = pack forward in that form [539 = product: + 128 = pack backward data on the matrix cores])"""
+    """dx of the unpack layer's conv3d for one kernel variant (development knob 1 = 300 + the P3_* bits of csrc/p3_plan.hpp)"""
     from mindtheedge_amd import kernels as K
     from mindtheedge_amd._lib import dev_library
     K.set_compute_dtype("bf16")
@@ -136,8 +135,8 @@ def _close_to_valu(got, ref):
 @pytest.mark.parametrize("C,B,H,W", [(32, 2, 16, 32), (32, 1, 17, 33), (32, 3, 8, 16), (32, 1, 1, 1), (32, 1, 9, 47), (64, 1, 12, 48), (64, 2, 5, 19),
                                       (64, 1, 4, 16), (32, 2, 96, 160), (128, 1, 7, 21), (128, 2, 8, 16), (256, 1, 5, 16), (256, 2, 3, 33)])
 def test_matrix_core_unpack3d_forward_matches_the_valu_stencil(C, B, H, W):
-    """conv3d(1 -> 4) + pixel shuffle on the same bf16 input: the fp32-VALU gather kernel (307) against the banded-operand MFMA form (315, C <= 64)
-    and the taps-in-K form with transposing LDS reads (539 = product, C <= 256)"""
+    """conv3d(1 -> 4) + pixel shuffle on the same bf16 input: the fp32-VALU gather kernel against the banded-operand MFMA form (+ P3_UNPACK_FWD, C <= 64)
+    and the taps-in-K form with transposing LDS reads (the product's, C <= 256); the knob values are 300 + the P3_* bits of csrc/p3_plan.hpp"""
     ref = _unpack_fwd(C, B, H, W, 307, seed=C + W)
     _close_to_valu(_unpack_fwd(C, B, H, W, PRODUCT, seed=C + W), ref)
     if C <= 64:
@@ -172,12 +171,14 @@ def _pack_fwd(C, B, H, W, knob, seed):
 
 @pytest.mark.parametrize("C,B,H,W", [(32, 2, 16, 32), (32, 1, 6, 70), (64, 1, 12, 40), (64, 2, 10, 6), (128, 1, 8, 36), (256, 1, 4, 34), (512, 1, 4, 8), (64, 16, 6, 64)])
 def test_matrix_core_pack3d_forward_matches_the_valu_stencil(C, B, H, W):
-    """space-to-depth + conv3d(1 -> 4): the taps-in-K MFMA form (depth slabs of 128; 539 = product) against the fp32-VALU LDS stencil (347)"""
+    """space-to-depth + conv3d(1 -> 4): the taps-in-K MFMA form (depth slabs of 128; the product's) against the fp32-VALU LDS stencil (P3_PACK_FWD_TAPS_K
+    cleared; knob values: 300 + the P3_* bits of csrc/p3_plan.hpp)"""
     _close_to_valu(_pack_fwd(C, B, H, W, PRODUCT, seed=C + H), _pack_fwd(C, B, H, W, 347, seed=C + H))
 
 
 def _pack_bwd_data(C, B, H, W, knob, seed):
-    """dx of the pack layer's conv3d for one kernel variant (knob 1: 411 = fp32-VALU LDS stencil, 539 = matrix cores [product], 555 = ... with the weights as one bf16 value)"""
+    """dx of the pack layer's conv3d for one kernel variant (knob 1 = 300 + the P3_* bits of csrc/p3_plan.hpp: without P3_PACK_BWD_DATA the fp32-VALU LDS
+    stencil, the product's matrix-core form, and that with P3_ONE_BF16_WEIGHT)"""
     from mindtheedge_amd import kernels as K
     from mindtheedge_amd._lib import dev_library
     K.set_compute_dtype("bf16")

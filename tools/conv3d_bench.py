@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """development aid (round 4): the conv3d(1 -> 4) data paths of the pack / unpack layers at their T8 shapes -- us per launch, algorithmic TB/s,
-cycles per output and SIMD -- for the kernel variants behind mte_debug_set(1, v): 300 = fp32-VALU LDS stencils, 300 + bits = matrix-core forms.
+cycles per output and SIMD -- for the kernel variants behind mte_debug_set(1, 300 + bits): the bits are the P3_* constants of csrc/p3_plan.hpp
+(no bit = fp32-VALU LDS stencils, P3_MFMA_DATA_PRODUCT = the product's matrix-core forms).
 Also prints the largest element-wise difference of each variant against the first one (same inputs).
 usage: conv3d_bench.py [variant ...]   (default: 300 411 539)"""
 import os
