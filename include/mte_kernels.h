@@ -503,6 +503,31 @@ int mte_image_resample_u8(const unsigned char* src, long src_stride, int crop_x,
 int mte_color_jitter_u8_to_f32(const unsigned char* in, int B, int H, int W, const float* factors, const int* order, int any_contrast,
                                unsigned long long* luma_sums, float* out, float* out_original, mte_stream_t stream);
 
+/* ---- sparse LiDAR input (utils/depth.py:366-467 augment_depth_values; datasets/gta_dataset.py:85-104 process_lidar), csrc/lidar_prep.hip
+ * Sparse maps are float32 [H,W] with 0 = no return, H * W < 2^30.  All arithmetic is double; results are rounded to float32 once, on the
+ * final store.  The perturbation runs in three stages that share `work` (mte_lidar_perturb_work_bytes(H, W) bytes, 8-byte aligned, content
+ * on entry ignored); its first two 32-bit words are the counts the host reads between the stages: work[0] = n, work[1] = n'.
+ * mte_lidar_index:   every pixel > 0 gets its ordinal k in raster order (np.where); n = their number.
+ * mte_lidar_perturb: n = the count read from work[0] (> 0; the kernels never walk past the device's own count), add_* = float64 [n] draws.
+ *   d' = add_d[k] + d * scale_d0;  i' = rint(i + add_i[k]), j' = rint(j + add_j[k]) (half to even);  key = i' + H * (j' - 1);
+ *   cell ii = key mod H (non-negative), jj = (key - ii) / H + 1: a row index outside [0, H) wraps into the neighbouring column and only
+ *   0 <= jj < W is tested.  Every point whose key is the smallest key of the map is discarded; among points with equal key the lowest
+ *   ordinal survives (the reference under a stable argsort; integer atomicMin, bit-reproducible).  Survivors with jj in range get the rank
+ *   m = their order by ordinal; n' = their number.
+ * mte_lidar_scatter: keep = uint8 [n_keep], n_keep = n' (0: keep may be null); out[ii,jj] = float32(d') for survivors with keep[m] == 1,
+ *   every other element of out is written as 0.  n == 0 (an empty map) writes zeros without reading `work`.
+ * mte_lidar_project: points float64 [3,N], K float64 [9] (row major), both on the device.  p = K P, p_norm = p / p[2]; a point is kept where
+ *   0 <= p_norm[0] < W and 0 <= p_norm[1] < H (false for non-finite quotients; points behind the camera pass when their quotients do), its
+ *   pixel is the truncation of p_norm, its value p[2]; the point with the highest index wins a shared pixel.  depth_map (float32 [H,W],
+ *   may be null): cells with lidar > 0 and sqrt((lidar - depth)^2) > 0.1 become 0.  winner_ws: H*W ints of scratch. */
+long mte_lidar_perturb_work_bytes(int H, int W);
+int mte_lidar_index(const float* depth, int H, int W, void* work, mte_stream_t stream);
+int mte_lidar_perturb(const float* depth, int H, int W, int n, double scale_d0, const double* add_i, const double* add_j, const double* add_d,
+                      void* work, mte_stream_t stream);
+int mte_lidar_scatter(int H, int W, int n, const unsigned char* keep, int n_keep, float* out, const void* work, mte_stream_t stream);
+int mte_lidar_project(const double* points, int N, const double* K, const float* depth_map, float* out, int H, int W, int* winner_ws,
+                      mte_stream_t stream);
+
 #ifdef MTE_DEV
 /* Development knobs for same-box A/B measurements (tools/sweep.sh) and kernel-variant cross-checks (tests/).  NOT part of the
  * integration surface: exported only by libmte_hip_dev.so, the -DMTE_DEV build of the same sources (mindtheedge_amd/_build.py);

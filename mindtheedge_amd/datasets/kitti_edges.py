@@ -116,8 +116,7 @@ def prepare_edge_sample(edge_maps_u8, normal_maps_u8, shape):
 # ---- a reader on top of the formats above -------------------------------------------------------------------------------
 # File decoding is host I/O (PIL / numpy, the reference uses PIL and cv2.imread); everything after it -- the crop, the LANCZOS
 # resize of the frame, colour jitter and ToTensor (image_prep.py), sparse resizes, target scaling, de-quantisation -- runs on the
-# device.  Not rebuilt: the colour matrix, LiDAR value perturbation (augment_depth_values), context frames, the .bin velodyne
-# projection (pass depth / lidar maps as 16-bit PNG or .npy).
+# device, and so do the LiDAR column's projection and perturbation (lidar_prep.py).  Not rebuilt: the colour matrix, context frames.
 
 def _read_gray_u8(path):
     """cv2.imread(path)[:, :, 0] of the reference for the 8-bit single-channel annotation PNGs."""
@@ -150,15 +149,24 @@ class KittiEdgeSplitDataset:
 
     jittering = (brightness, contrast, saturation, hue) draws the reference's colour jitter per sample from Python's ``random``
     (the sample then also carries the un-jittered ``rgb_original``); crop_train_borders crops rgb, depth, edge and normal
-    before the resize like crop_sample.  Both default to () = off."""
+    before the resize like crop_sample.  Both default to () = off.
 
-    def __init__(self, split_file, image_shape, device='cuda', root='', jittering=(), crop_train_borders=()):
+    input_depth_type (None, '' or [''] = off) switches the split's LiDAR column on (.png / .npy / velodyne .bin, lidar_prep.py): cropped
+    and resized like the depth map it becomes ``lidar`` and ``input_depth``; with lidar_scale and lidar_add both non-empty (2 x 3 ranges,
+    reference augment_depth_values) the ``input_depth`` copy is perturbed with lidar_drop_rate, drawing from ``np.random``."""
+
+    def __init__(self, split_file, image_shape, device='cuda', root='', jittering=(), crop_train_borders=(), input_depth_type=None,
+                 lidar_scale=(), lidar_add=(), lidar_drop_rate=0.0):
         self.records = read_split(split_file)
         self.shape = (int(image_shape[0]), int(image_shape[1]))
         self.device = torch.device(device)
         self.root = root
         self.jittering = tuple(jittering or ())
         self.crop_train_borders = tuple(crop_train_borders or ())
+        types = [input_depth_type] if isinstance(input_depth_type, str) else list(input_depth_type or [])
+        self.with_input_depth = any(t not in (None, '') for t in types)
+        self.lidar_scale, self.lidar_add = tuple(lidar_scale or ()), tuple(lidar_add or ())
+        self.lidar_drop_rate = float(lidar_drop_rate)
 
     def __len__(self):
         return len(self.records)
@@ -191,11 +199,23 @@ class KittiEdgeSplitDataset:
             sample['rgb'], sample['rgb_original'] = rgb[0], original[0]
         else:
             sample['rgb'] = ip.color_jitter_to_tensor(frame.unsqueeze(0))[0]
+        d = None
         if rec.get('depth'):
-            d = read_png_depth(self._p(rec['depth']))
+            d = d_full = read_png_depth(self._p(rec['depth']))
             if borders is not None:
                 d = np.ascontiguousarray(d[borders[1]:borders[3], borders[0]:borders[2]])
             sample['depth'] = resize_depth_preserve(torch.from_numpy(d).to(self.device), self.shape).unsqueeze(0)
+        if self.with_input_depth and rec.get('lidar'):
+            from . import lidar_prep as lp
+            lidar = lp.read_lidar_map(self._p(rec['lidar']), self.device, depth_map=d_full if d is not None else None)   # gta_dataset.py:368-382
+            if borders is not None:
+                lidar = lidar[borders[1]:borders[3], borders[0]:borders[2]].contiguous()
+            lidar = resize_depth_preserve(lidar, self.shape)
+            sample['lidar'] = lidar.unsqueeze(0)
+            if len(self.lidar_scale) > 0 and len(self.lidar_add) > 0:        # transforms.py:46-48: only the network's input is perturbed
+                sample['input_depth'] = lp.augment_depth_values(lidar, self.lidar_scale, self.lidar_add, self.lidar_drop_rate).unsqueeze(0)
+            else:
+                sample['input_depth'] = lidar.clone().unsqueeze(0)
         edges, normals = [], []
         # crop_sample crops 'edge' and 'normal' only: the coarser scales keep their frame (augmentations.py:512-518)
         if rec.get('edge'):
@@ -245,7 +265,8 @@ def _as_tuple(v):
 def make_loader(config, rank, world):
     """``train_edges.py --data mindtheedge_amd.datasets.kitti_edges:make_loader``: config.datasets.train.split[0] is the
     8-column split file, config.datasets.train.path[0] (optional) the root folder of its relative paths;
-    config.datasets.augmentation.jittering / .crop_train_borders as in the reference (default (): off)."""
+    config.datasets.augmentation.jittering / .crop_train_borders as in the reference (default (): off);
+    config.datasets.train.input_depth_type and config.datasets.augmentation.lidar_scale / lidar_add / lidar_drop_rate for the LiDAR column."""
     tr = config.datasets.train
     shape = config.datasets.augmentation.image_shape
     shape = eval(shape) if isinstance(shape, str) else tuple(shape)
@@ -253,5 +274,7 @@ def make_loader(config, rank, world):
     split = tr['split'][0] if isinstance(tr['split'], (list, tuple)) else tr['split']
     aug = config.datasets.augmentation
     ds = KittiEdgeSplitDataset(split, shape, device=torch.device('cuda', torch.cuda.current_device()), root=root,
-                               jittering=_as_tuple(aug.get('jittering')), crop_train_borders=_as_tuple(aug.get('crop_train_borders')))
+                               jittering=_as_tuple(aug.get('jittering')), crop_train_borders=_as_tuple(aug.get('crop_train_borders')),
+                               input_depth_type=tr.get('input_depth_type'), lidar_scale=_as_tuple(aug.get('lidar_scale')),
+                               lidar_add=_as_tuple(aug.get('lidar_add')), lidar_drop_rate=float(aug.get('lidar_drop_rate') or 0.0))
     return SplitLoader(ds, int(tr.batch_size), rank, world)

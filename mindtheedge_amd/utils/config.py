@@ -37,7 +37,11 @@ _DEFAULTS = {
               'depth_edge_loss_pos_to_neg_weight': 1.0},
     # jittering / crop_train_borders: () = off.  The reference's default_config.py:166 jitters with (0.2, 0.2, 0.2, 0.05) and crops
     # nothing; a run that wants the reference's recipe sets  datasets.augmentation.jittering: [0.2, 0.2, 0.2, 0.05]  in its YAML.
-    'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': ()}, 'train': {'batch_size': 8}},
+    # lidar_scale / lidar_add / lidar_drop_rate, input_depth_type, is_infer_rgb / is_infer_lidar: default_config.py:169-171,184,217,223-224
+    'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': (),
+                                  'lidar_scale': (), 'lidar_add': (), 'lidar_drop_rate': 0.0},
+                 'train': {'batch_size': 8, 'input_depth_type': ['']},
+                 'test': {'input_depth_type': [''], 'is_infer_rgb': True, 'is_infer_lidar': True}},
     'checkpoint': {'filepath': '', 'save_top_k': -1},
 }
 

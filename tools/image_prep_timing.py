@@ -7,6 +7,7 @@
 
     python tools/image_prep_timing.py [--reps 200] [--out profiles/image_prep.txt]
     python tools/image_prep_timing.py --dataset-only --tree <checkout of the parent commit>      ds[i] end to end on another tree
+    python tools/image_prep_timing.py --lidar [--out profiles/lidar_prep.txt]      ds[i] end to end with and without the LiDAR column
 """
 import argparse
 import os
@@ -77,17 +78,60 @@ def dataset_timing(args):
             f.write(text + "\n")
 
 
+def lidar_timing(args):
+    """ds[i] end to end on KITTI-size files without the LiDAR column, with it, and with its perturbation; then the device calls alone"""
+    import tempfile
+    from mindtheedge_amd.datasets.kitti_edges import KittiEdgeSplitDataset, resize_depth_preserve
+    from mindtheedge_amd.datasets import lidar_prep as lp
+    g = np.random.default_rng(0)
+    scale, add = ((1, 1, 1), (1, 1, 1.1)), ((0, 0, 0), (1.5, 1.5, 0.5))
+    reps = max(10, args.reps // 10)
+    lines = ["LiDAR column, %d x %d -> %d x %d at 5 %% density, batch %d, %s" % (SRC + DST + (B, torch.cuda.get_device_name(0)))]
+    with tempfile.TemporaryDirectory() as tmp:
+        rows = []
+        for i in range(B):
+            Image.fromarray(g.integers(0, 256, SRC + (3,), dtype=np.uint8)).save(os.path.join(tmp, "rgb%d.png" % i), compress_level=1)
+            raw = ((g.random(SRC) < 0.05) * (256 + g.integers(0, 79 * 256, SRC))).astype(np.uint16)
+            raw[0, 0] = 300
+            Image.fromarray(raw).save(os.path.join(tmp, "lidar%d.png" % i), compress_level=1)
+            rows.append("rgb%d.png None None lidar%d.png None None None None\n" % (i, i))
+        split = os.path.join(tmp, "split.txt")
+        open(split, "w").writelines(rows)
+        for name, kw in [("without the column", {}), ("with the column (read + resize_depth_preserve)", {"input_depth_type": ["velodyne"]}),
+                         ("with the column, perturbed (two host reads per sample)", {"input_depth_type": ["velodyne"], "lidar_scale": scale,
+                                                                                   "lidar_add": add, "lidar_drop_rate": 0.1})]:
+            ds = KittiEdgeSplitDataset(split, DST, root=tmp, **kw)
+            med, best = host_ms(lambda: [ds[i] for i in range(B)], reps)
+            lines.append("ds[i] for a batch of 8, %-56s median %8.3f ms   min %8.3f ms   (host clock around a synchronise, %d reps)" % (name, med, best, reps))
+    depth = torch.from_numpy(((g.random(DST) < 0.05) * (1 + 79 * g.random(DST))).astype(np.float32)).cuda()
+    med, best = host_ms(lambda: lp.augment_depth_values(depth, scale, add, 0.1), args.reps)
+    lines.append("augment_depth_values alone, %d returns (draws, uploads, 10 launches, two host reads)   median %8.3f ms   min %8.3f ms" % (int((depth > 0).sum()), med, best))
+    med, best = event_ms(lambda: resize_depth_preserve(depth, DST), args.reps)
+    lines.append("resize_depth_preserve alone (HIP events)   median %7.4f ms  min %7.4f ms" % (med, best))
+    pts = np.stack([g.uniform(-30, 30, 100000), g.uniform(-8, 8, 100000), g.uniform(0.5, 80, 100000)])
+    med, best = host_ms(lambda: lp.project_lidar(pts, lp.GTA_INTRINSICS), args.reps)
+    lines.append("project_lidar, 100000 points into 1080 x 1920 (upload included)   median %8.3f ms   min %8.3f ms" % (med, best))
+    text = "\n".join(lines)
+    print(text)
+    if args.out:
+        with open(args.out, "w") as f:
+            f.write(text + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--out", default="")
     ap.add_argument("--tree", default="")
     ap.add_argument("--dataset-only", action="store_true")
+    ap.add_argument("--lidar", action="store_true", help="time the dataset's LiDAR column instead")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("needs the GPU: a timing taken without one says nothing")
     if args.dataset_only:
         return dataset_timing(args)
+    if args.lidar:
+        return lidar_timing(args)
     from mindtheedge_amd.datasets import image_prep as ip
     g = np.random.default_rng(0)
     frames = [g.integers(0, 256, SRC + (3,), dtype=np.uint8) for _ in range(B)]
