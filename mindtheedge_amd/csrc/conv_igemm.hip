@@ -1626,15 +1626,15 @@ extern "C" {
 
 #ifdef MTE_DEV
 // development knobs (libmte_hip_dev.so only, -DMTE_DEV): the implicit-GEMM keys are IgemmKnobs (conv_plan.hpp); key 1 = conv3d pack / unpack
-// stencils (P3Knobs, p3_plan.hpp: the value's range names the member).  Not part of the product contract.
+// stencils (P3Knobs, p3_plan.hpp: the value's range names the member), key 11 = LDS-patch convolution (PatchKnobs, patch_plan.hpp: likewise).  Not part of the product contract.
 extern "C" int mtei_set_pack3d_lds(int value);      // P3Knobs (p3_plan.hpp)
 extern "C" int mtei_set_gn(int key, int value);
-extern "C" int mtei_set_patch_tall(int v);
+extern "C" int mtei_set_patch_tall(int v);           // PatchKnobs (patch_plan.hpp)
 extern "C" int mtei_set_tap_wgrad(int v);            // tap_wgrad.hip
 extern "C" int mtei_set_head_mfma(int v);
 extern int g_wgrad9, g_wgrad9_wgs;
 int mte_debug_set(int key, int value) {
-    if (key == MTE_KNOB_IGEMM_RESET) (void)mtei_set_pack3d_lds(-1);     // 33 also puts the conv3d pack / unpack knobs back (P3_KNOB_RESET)
+    if (key == MTE_KNOB_IGEMM_RESET) { (void)mtei_set_pack3d_lds(-1); (void)mtei_set_patch_tall(-1); }   // 33 also puts the conv3d pack / unpack and the LDS-patch knobs back (P3_KNOB_RESET, PATCH_KNOB_RESET)
     if (igemm_knob_set(g_igemm_knobs, key, value)) return MTE_OK;      // keys 0, 6, 7, 15, 17, 19, 21, 23, 24, 28, 29, 32; 33 = all of them back to their defaults
     if (key == 26) { g_wgrad9 = value; return MTE_OK; }
     if (key == 27) { g_wgrad9_wgs = value; return MTE_OK; }

@@ -16,6 +16,7 @@
 //
 // Reference ops replaced: nn.Conv2d + ConstantPad2d of Conv2D / ResidualConv (layers01.py:29-31,61) and their autograd.
 #include "common.hpp"
+#include "patch_plan.hpp"
 #include <type_traits>
 
 // In-kernel phase stamps of the forward kernels: a separate diagnostic build only (-DMTE_STAMPS, tools/patch_stamps.py); no stamp executes in
@@ -1076,185 +1077,110 @@ __global__ __launch_bounds__(NW * 64) void conv_patch_wgrad_kernel(PatchWgradArg
     }
 }
 
-// Workgroup groups of the weight-gradient launches WHEN THEY SHARE THE CHIP with the data-gradient chain (MTE_OPT_WGRAD_SHARES_CHIP; round 5, same-box
-// step times with the two-stream schedule, profiles/r05_side_queue_width.txt):
-// 512 -> 256 groups: 23.25 -> 23.16 ms per step (192: the same, 128: 23.60); the wide (65..128-output) variant 256 -> 128: a further -0.08 ms.  Fewer,
-// longer workgroups leave CUs to the data-gradient chain and halve the slabs the unpack pass adds up.
-// (end of round 5, after the kernel's instruction diet: 256 -> 22.75 ms per step, 192 -> 22.67, 160 -> 22.65, 128 -> 22.95 on one box; 23.24 / 23.13 / -- on another: 192)
-#ifndef MTE_PATCH_WGRAD_WGS
-#define MTE_PATCH_WGRAD_WGS 192
-#endif
-#ifndef MTE_PATCH_WGRAD_WIDE_WGS
-#define MTE_PATCH_WGRAD_WIDE_WGS 128
-#endif
-int g_patch_wgrad_wgs = MTE_PATCH_WGRAD_WGS;         // development knob (mte_debug_set(12, v))
-int g_patch_tall = 1;                                // development knob (mte_debug_set(11, v))
+static_assert(TH == PATCH_TH && TW == PATCH_TW, "patch_plan.hpp counts the tiles the kernels walk");
 
-#ifdef MTE_PATCH_FWD1
-int g_patch_fwd2 = 0;                                // (diagnostic builds: tools/patch_stamps.py v1)
-#else
-int g_patch_fwd2 = 1;
-#endif
-//                               // development knob (mte_debug_set(11, 400 + v)): 0 = the first form of the forward kernel
+PatchKnobs g_patch_knobs;                            // development knobs (mte_debug_set(11, v), and key 33 as v = PATCH_KNOB_RESET -> mtei_set_patch_tall)
 
-// Round 6: every forward form runs on v_mfma_f32_16x16x32_bf16 (M16); the 32x32x16 forms of rounds 1-5 are instantiated in the development library only
-// (knobs below; tests/test_gpu_conv_variants.py compares the two).  Same-box A/B per layer: profiles/r06_m16_ab.txt, profiles/r06_inloop_clock.txt.
-int g_patch_m16 = 1;                                 // development knob (mte_debug_set(11, 500 + v)): 0 = the 5x5 / 7x7 second form on v_mfma_f32_32x32x16_bf16
-int g_patch_m16_3 = 1;                               // development knob (mte_debug_set(11, 700 + v)): 0 = the 3x3 / 1x1 second form on v_mfma_f32_32x32x16_bf16
-int g_patch_m16_f1 = 1;                              // development knob (mte_debug_set(11, 600 + v)): 0 = the first form on v_mfma_f32_32x32x16_bf16
+template <auto K> int launch_patch_fwd(const PatchPlan& pl, const PatchArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(K, dim3(pl.grid_x), dim3(pl.block), 0, st, a);
+    return mte_check_launch();
+}
+template <auto K> int launch_patch_wgrad(const PatchPlan& pl, const PatchWgradArgs& a, hipStream_t st) {
+    if (mte_allow_lds<K>((int)pl.lds) != MTE_OK) return MTE_ERR_LAUNCH;
+    hipLaunchKernelGGL(K, dim3(pl.grid_x, pl.grid_y), dim3(pl.block), pl.lds, st, a);
+    return mte_check_launch();
+}
 
-// one forward launch: second (F2) or first form of the kernel; accumulating or not (a.accum; never with R1 / EXTRA); MFMA shape
-template <bool F2, int K, int NT, bool TALL, bool R1 = false, bool EXTRA = false>
-static void launch_form(const PatchArgs& a, long tiles, hipStream_t st, bool m16) {
-    const dim3 g((unsigned)tiles), b(256);
-    static_assert(F2 || !R1, "the rank-1 term rides the second form");
+// Pick the instance, launch.  Every instance plan_patch can name stands here once (the key and the instance from the same argument list); the cases stand in
+// the order in which the launch functions used to name the instances: the order of the kernels in the code object follows it.  _32: the 32x32x16 MFMA forms
+// (M16 = false), which only the development library has -- the product has no way to set the knobs that ask for them.
+#define PATCH_FWD(...) case patch_fwd_key(__VA_ARGS__): return launch_patch_fwd<conv_patch_fwd_kernel<__VA_ARGS__>>(pl, a, st);
+#define PATCH_FWD2(...) case patch_fwd2_key(__VA_ARGS__): return launch_patch_fwd<conv_patch_fwd2_kernel<__VA_ARGS__>>(pl, a, st);
+#define PATCH_WGRAD(...) case patch_wgrad_key(__VA_ARGS__): return launch_patch_wgrad<conv_patch_wgrad_kernel<__VA_ARGS__>>(pl, a, st);
 #ifdef MTE_DEV
-    if (!m16) {
-        if constexpr (F2) {
-            if constexpr (!R1 && !EXTRA) { if (a.accum) { hipLaunchKernelGGL((conv_patch_fwd2_kernel<K, NT, TALL, false, true>), g, b, 0, st, a); return; } }
-            hipLaunchKernelGGL((conv_patch_fwd2_kernel<K, NT, TALL, R1, false, EXTRA>), g, b, 0, st, a);
-        } else {
-            if constexpr (!EXTRA) { if (a.accum) { hipLaunchKernelGGL((conv_patch_fwd_kernel<K, NT, TALL, true>), g, b, 0, st, a); return; } }
-            hipLaunchKernelGGL((conv_patch_fwd_kernel<K, NT, TALL, false, EXTRA>), g, b, 0, st, a);
-        }
-        return;
-    }
+#define PATCH_FWD_32(...) PATCH_FWD(__VA_ARGS__, false)
+#define PATCH_FWD2_32(...) PATCH_FWD2(__VA_ARGS__, false)
+#else
+#define PATCH_FWD_32(...)
+#define PATCH_FWD2_32(...)
 #endif
-    (void)m16;
-    if constexpr (F2) {
-        if constexpr (!R1 && !EXTRA) { if (a.accum) { hipLaunchKernelGGL((conv_patch_fwd2_kernel<K, NT, TALL, false, true, false, true>), g, b, 0, st, a); return; } }
-        hipLaunchKernelGGL((conv_patch_fwd2_kernel<K, NT, TALL, R1, false, EXTRA, true>), g, b, 0, st, a);
-    } else {
-        if constexpr (!EXTRA) { if (a.accum) { hipLaunchKernelGGL((conv_patch_fwd_kernel<K, NT, TALL, true, false, true>), g, b, 0, st, a); return; } }
-        hipLaunchKernelGGL((conv_patch_fwd_kernel<K, NT, TALL, false, EXTRA, true>), g, b, 0, st, a);
-    }
-}
-
-template <int K, int NT> int launch_fwd(const PatchArgs& a, hipStream_t st, int* tile_rows = nullptr) {
-    // the second form addresses the input through a buffer descriptor (< 2 GiB)
-    // Same-box A/B over the network's shapes (tools/conv_shape_bench.py): 7x7 -12..-15 %, 5x5 -8..-12 %, 3x3 with 32 outputs -4..-12 %, 3x3
-    // with 64 outputs -8 % from three slices on; with one or two slices the first form wins by 8-15 % (167 VGPRs, three workgroups per CU,
-    // against 244), and the 1x1 layers are HBM-bound either way
-    const bool v2 = g_patch_fwd2 && (K >= 5 || (K == 3 && (NT == 1 || a.Cin_p > 64))) &&
-                    (((long)a.B * a.H * a.W - 1) * a.ldx + a.Cin_p) * 2 < 0x7ff00000L && ((uintptr_t)a.bias & 15) == 0;   // (it reads the bias in 16-byte groups)
-    const bool m16 = v2 ? (K >= 5 ? g_patch_m16 : g_patch_m16_3) != 0 : g_patch_m16_f1 != 0;
-    if constexpr (NT == 1) {
-        if (g_patch_tall && (a.Cin_p <= 32 || K <= 3) && a.H >= 16) {
-            if (tile_rows) *tile_rows = 16;
-            const long tiles = (long)(a.W / TW) * ((a.H + 15) / 16) * a.B;
-            if (v2) launch_form<true, K, NT, true>(a, tiles, st, m16);
-            else launch_form<false, K, NT, true>(a, tiles, st, m16);
-            return mte_check_launch();
-        }
-    }
-    if (tile_rows) *tile_rows = TH;
-    const long tiles = (long)(a.W / TW) * ((a.H + TH - 1) / TH) * a.B;
-    if (v2) launch_form<true, K, NT, false>(a, tiles, st, m16);
-    else launch_form<false, K, NT, false>(a, tiles, st, m16);
-    return mte_check_launch();
-}
-template <int NT> int dispatch_fwd(const PatchArgs& a, int K, hipStream_t st, int* tile_rows = nullptr) {
-    switch (K) {
-        case 1: return launch_fwd<1, NT>(a, st, tile_rows);
-        case 3: return launch_fwd<3, NT>(a, st, tile_rows);
-        case 5: return launch_fwd<5, NT>(a, st, tile_rows);
-        case 7: return launch_fwd<7, NT>(a, st, tile_rows);
+int launch_patch_plan(const PatchPlan& pl, const PatchArgs& a, hipStream_t st) {
+    if (pl.rc != MTE_OK) return pl.rc;
+    switch (patch_key(pl)) {      // conv_patch_fwd2_kernel<K, NT, TALL, R1, ACC, EXTRA, M16>, conv_patch_fwd_kernel<K, NT, TALL, ACC, EXTRA, M16>
+    PATCH_FWD_32(1, 1, true, true, false) PATCH_FWD_32(1, 1, true, false, false) PATCH_FWD(1, 1, true, true, false, true) PATCH_FWD(1, 1, true, false, false, true)
+    PATCH_FWD_32(1, 1, false, true, false) PATCH_FWD_32(1, 1, false, false, false) PATCH_FWD(1, 1, false, true, false, true) PATCH_FWD(1, 1, false, false, false, true)
+    PATCH_FWD2_32(3, 1, true, false, true, false) PATCH_FWD2_32(3, 1, true, false, false, false) PATCH_FWD2(3, 1, true, false, true, false, true) PATCH_FWD2(3, 1, true, false, false, false, true)
+    PATCH_FWD_32(3, 1, true, true, false) PATCH_FWD_32(3, 1, true, false, false) PATCH_FWD(3, 1, true, true, false, true) PATCH_FWD(3, 1, true, false, false, true)
+    PATCH_FWD2_32(3, 1, false, false, true, false) PATCH_FWD2_32(3, 1, false, false, false, false) PATCH_FWD2(3, 1, false, false, true, false, true) PATCH_FWD2(3, 1, false, false, false, false, true)
+    PATCH_FWD_32(3, 1, false, true, false) PATCH_FWD_32(3, 1, false, false, false) PATCH_FWD(3, 1, false, true, false, true) PATCH_FWD(3, 1, false, false, false, true)
+    PATCH_FWD2_32(5, 1, true, false, true, false) PATCH_FWD2_32(5, 1, true, false, false, false) PATCH_FWD2(5, 1, true, false, true, false, true) PATCH_FWD2(5, 1, true, false, false, false, true)
+    PATCH_FWD_32(5, 1, true, true, false) PATCH_FWD_32(5, 1, true, false, false) PATCH_FWD(5, 1, true, true, false, true) PATCH_FWD(5, 1, true, false, false, true)
+    PATCH_FWD2_32(5, 1, false, false, true, false) PATCH_FWD2_32(5, 1, false, false, false, false) PATCH_FWD2(5, 1, false, false, true, false, true) PATCH_FWD2(5, 1, false, false, false, false, true)
+    PATCH_FWD_32(5, 1, false, true, false) PATCH_FWD_32(5, 1, false, false, false) PATCH_FWD(5, 1, false, true, false, true) PATCH_FWD(5, 1, false, false, false, true)
+    PATCH_FWD2_32(7, 1, true, false, true, false) PATCH_FWD2_32(7, 1, true, false, false, false) PATCH_FWD2(7, 1, true, false, true, false, true) PATCH_FWD2(7, 1, true, false, false, false, true)
+    PATCH_FWD_32(7, 1, true, true, false) PATCH_FWD_32(7, 1, true, false, false) PATCH_FWD(7, 1, true, true, false, true) PATCH_FWD(7, 1, true, false, false, true)
+    PATCH_FWD2_32(7, 1, false, false, true, false) PATCH_FWD2_32(7, 1, false, false, false, false) PATCH_FWD2(7, 1, false, false, true, false, true) PATCH_FWD2(7, 1, false, false, false, false, true)
+    PATCH_FWD_32(7, 1, false, true, false) PATCH_FWD_32(7, 1, false, false, false) PATCH_FWD(7, 1, false, true, false, true) PATCH_FWD(7, 1, false, false, false, true)
+    PATCH_FWD_32(1, 2, false, true, false) PATCH_FWD_32(1, 2, false, false, false) PATCH_FWD(1, 2, false, true, false, true) PATCH_FWD(1, 2, false, false, false, true)
+    PATCH_FWD2_32(3, 2, false, false, true, false) PATCH_FWD2_32(3, 2, false, false, false, false) PATCH_FWD2(3, 2, false, false, true, false, true) PATCH_FWD2(3, 2, false, false, false, false, true)
+    PATCH_FWD_32(3, 2, false, true, false) PATCH_FWD_32(3, 2, false, false, false) PATCH_FWD(3, 2, false, true, false, true) PATCH_FWD(3, 2, false, false, false, true)
+    PATCH_FWD2_32(5, 2, false, false, true, false) PATCH_FWD2_32(5, 2, false, false, false, false) PATCH_FWD2(5, 2, false, false, true, false, true) PATCH_FWD2(5, 2, false, false, false, false, true)
+    PATCH_FWD_32(5, 2, false, true, false) PATCH_FWD_32(5, 2, false, false, false) PATCH_FWD(5, 2, false, true, false, true) PATCH_FWD(5, 2, false, false, false, true)
+    PATCH_FWD2_32(3, 1, true, true, false, false) PATCH_FWD2(3, 1, true, true, false, false, true)
+    PATCH_FWD2_32(3, 1, false, true, false, false) PATCH_FWD2(3, 1, false, true, false, false, true)
+    PATCH_FWD2_32(3, 2, false, true, false, false) PATCH_FWD2(3, 2, false, true, false, false, true)
+    PATCH_FWD2_32(3, 1, true, false, false, true) PATCH_FWD2(3, 1, true, false, false, true, true)
+    PATCH_FWD_32(3, 1, true, false, true) PATCH_FWD(3, 1, true, false, true, true)
+    PATCH_FWD2_32(3, 1, false, false, false, true) PATCH_FWD2(3, 1, false, false, false, true, true)
+    PATCH_FWD_32(3, 1, false, false, true) PATCH_FWD(3, 1, false, false, true, true)
+    PATCH_FWD2_32(3, 2, false, false, false, true) PATCH_FWD2(3, 2, false, false, false, true, true)
+    PATCH_FWD_32(3, 2, false, false, true) PATCH_FWD(3, 2, false, false, true, true)
     }
     return MTE_ERR_UNSUPPORTED;
 }
-
-int g_patch_wgrad_8w = 1;                            // development knob (mte_debug_set(11, 200 + v)): 0 = four waves per workgroup everywhere
-int g_patch_wgrad_wide = 1;                          // development knob (mte_debug_set(11, 300 + v)): 0 = 65..128 output channels stay on the generic weight gradient
-
-template <int K, int NT, int SL, int NW = 4, int NH = 1, int THW = 8> int launch_wgrad_sl(PatchWgradArgs a, hipStream_t st, int parts_cap, int* parts_out) {
-    constexpr int TH = THW;
-    constexpr int PH = TH + K - 1, PW = TW + K - 1;
-    constexpr int XRS = SL == 1 ? 64 : 192, YRS = NT * NH == 1 ? 64 : (NT * NH == 2 ? 192 : 320);
-    const size_t lds = PH * PW * XRS + TH * TW * YRS;
-    const int nslices = (a.Cin_p + 32 * SL - 1) / (32 * SL);
-    const long ntiles = (long)(a.W / TW) * ((a.H + TH - 1) / TH) * a.B;
-    // ~2 workgroups per CU in total; the 147 KB wide variant (NH = 2) holds one per CU: one round of workgroups, half the slabs to add up
-    // (alone on the chip -- MTE_OPT_WGRAD_SHARES_CHIP off -- twice the groups: the round-4 geometry)
-    const int want = (NH == 2 ? MTE_PATCH_WGRAD_WIDE_WGS : g_patch_wgrad_wgs) * (g_mte_wgrad_shared ? 1 : 2);
-    long groups = (want + nslices - 1) / nslices;
-    if (groups > ntiles) groups = ntiles;
-    if (groups > parts_cap) groups = parts_cap < 1 ? 1 : parts_cap;   // one slab per workgroup group, always (round 4: no fp32-atomic combine on this launch path)
-    a.groups = (int)groups;
-    if (mte_allow_lds<conv_patch_wgrad_kernel<K, NT, SL, NW, NH, THW>>((int)lds) != MTE_OK) return MTE_ERR_LAUNCH;
-    if (a.groups > 1 && a.groups <= parts_cap) {                // one partial gradient per group, summed by the unpack pass
-        a.part_stride = (long)a.N * K * K * a.Cin_p;
-        if (parts_out) *parts_out = a.groups;
-    } else {
-        a.part_stride = 0;
-        if (parts_out) *parts_out = 1;
-        if (mte_memset_async(a.dw, 0, sizeof(float) * (size_t)a.N * K * K * a.Cin_p, st) != hipSuccess) return MTE_ERR_LAUNCH;
-    }
-    hipLaunchKernelGGL((conv_patch_wgrad_kernel<K, NT, SL, NW, NH, THW>), dim3((unsigned)groups, nslices), dim3(NW * 64), lds, st, a);
-    return mte_check_launch();
-}
-template <int K, int NT> int launch_wgrad(const PatchWgradArgs& a, hipStream_t st, int parts_cap, int* parts_out) {
-    // two slices per workgroup where the accumulators still fit (3x3 and 1x1; 5x5 with C_out <= 32) and there is more than one slice
-    // eight waves (two per SIMD on the one workgroup a CU holds) where a wave still gets enough accumulator units: two output
-    // tiles per unit, or >= 32 units.  Same-box A/B per launch: 7x7 32->32 @384x1280 0.510 -> 0.388 ms, 3x3 64->64 @192x640
-    // 0.146 -> 0.108, 5x5 256->64 @96x320 0.272 -> 0.205; the one-tile launches with 18 / 25 units lose 14-20 % and stay on four.
-    if constexpr (K == 3 && NT == 1) {
-        // 65..96 input channels (iconv1: the 72-channel decoder concat): all three 32-channel slices in ONE workgroup -- the 192-byte
-        // pixel rows of the two-slice layout are exactly full, dy is read once instead of once per slice pair (0.40 -> 0.29 ms)
-        if (a.Cin_p > 64 && a.Cin_p <= 96 && g_patch_wgrad_8w) return launch_wgrad_sl<K, NT, 3, 8>(a, st, parts_cap, parts_out);
-    }
-    if constexpr (K == 3 && NT == 2) {
-        // round 6: the same for 64 outputs (iconv2: the 96-channel concat @192x640) -- 27 (tap, slice) units over 8 waves instead of two slice groups of 18, the
-        // second one half empty: a third fewer MFMA steps (0.191 -> 0.147 ms, profiles/r06_lowres_split.txt; 4-row tiles: with 8 rows the staged next tile pushed it past 256 VGPRs)
-        if (a.Cin_p > 64 && a.Cin_p <= 96 && g_patch_wgrad_8w) return launch_wgrad_sl<K, NT, 3, 8, 1, 4>(a, st, parts_cap, parts_out);
-    }
-    if constexpr (K <= 3 || (K == 5 && NT == 1)) {
-        if (a.Cin_p > 32) {
-            if constexpr (K * K * 2 >= 16 && (NT == 2 || K * K * 2 >= 32)) {
-                if (g_patch_wgrad_8w) return launch_wgrad_sl<K, NT, 2, 8>(a, st, parts_cap, parts_out);
-            }
-            return launch_wgrad_sl<K, NT, 2>(a, st, parts_cap, parts_out);
-        }
-    }
-    if constexpr (K * K >= 16 && (NT == 2 || K * K >= 32)) {
-        if (g_patch_wgrad_8w) return launch_wgrad_sl<K, NT, 1, 8>(a, st, parts_cap, parts_out);
-    }
-    return launch_wgrad_sl<K, NT, 1>(a, st, parts_cap, parts_out);
-}
-template <int NT> int dispatch_wgrad(const PatchWgradArgs& a, int K, hipStream_t st, int parts_cap, int* parts_out) {
-    switch (K) {
-        case 1: return launch_wgrad<1, NT>(a, st, parts_cap, parts_out);
-        case 3: return launch_wgrad<3, NT>(a, st, parts_cap, parts_out);
-        case 5: return launch_wgrad<5, NT>(a, st, parts_cap, parts_out);
-        case 7: return launch_wgrad<7, NT>(a, st, parts_cap, parts_out);
+// the weight gradient: clear dw where the groups add into it, else one slab per group
+int launch_patch_plan(const PatchPlan& pl, PatchWgradArgs a, hipStream_t st) {
+    if (pl.rc != MTE_OK) return pl.rc;
+    a.groups = pl.groups; a.part_stride = pl.part_stride;
+    if (pl.clear_bytes && mte_memset_async(a.dw, 0, pl.clear_bytes, st) != hipSuccess) return MTE_ERR_LAUNCH;
+    switch (patch_key(pl)) {      // conv_patch_wgrad_kernel<K, NT, SL, NW, NH, THW>
+    PATCH_WGRAD(3, 2, 2, 8, 2, 4)
+    PATCH_WGRAD(1, 1, 2, 4, 1, 8) PATCH_WGRAD(1, 1, 1, 4, 1, 8) PATCH_WGRAD(3, 1, 3, 8, 1, 8) PATCH_WGRAD(3, 1, 2, 4, 1, 8)
+    PATCH_WGRAD(3, 1, 1, 4, 1, 8) PATCH_WGRAD(5, 1, 2, 8, 1, 8) PATCH_WGRAD(5, 1, 2, 4, 1, 8) PATCH_WGRAD(5, 1, 1, 4, 1, 8)
+    PATCH_WGRAD(7, 1, 1, 8, 1, 8) PATCH_WGRAD(7, 1, 1, 4, 1, 8)
+    PATCH_WGRAD(1, 2, 2, 4, 1, 8) PATCH_WGRAD(1, 2, 1, 4, 1, 8) PATCH_WGRAD(3, 2, 3, 8, 1, 4) PATCH_WGRAD(3, 2, 2, 8, 1, 8)
+    PATCH_WGRAD(3, 2, 2, 4, 1, 8) PATCH_WGRAD(3, 2, 1, 4, 1, 8) PATCH_WGRAD(5, 2, 1, 8, 1, 8) PATCH_WGRAD(5, 2, 1, 4, 1, 8)
     }
     return MTE_ERR_UNSUPPORTED;
 }
+#undef PATCH_FWD
+#undef PATCH_FWD2
+#undef PATCH_WGRAD
+#undef PATCH_FWD_32
+#undef PATCH_FWD2_32
 
-// weight gradient only: 65..128 output channels, 3x3, at least one 64-channel slice pair (the wide variant of conv_patch_wgrad_kernel)
-inline bool patch_wgrad_wide_ok(int W, int Cin_p, int N, int KH, int KW) {
-    return g_patch_wgrad_wide && W % TW == 0 && Cin_p % 8 == 0 && Cin_p >= 64 && N % 8 == 0 && N > 64 && N <= 128 && KH == 3 && KW == 3;
-}
-inline bool patch_shape_ok(int W, int Cin_p, int N, int KH, int KW) {
-    if (KH == 7 && N > 32) return false;             // 13 taps x 2 tiles of accumulators per wave would spill in wgrad
-    return W % TW == 0 && Cin_p % 8 == 0 && N % 8 == 0 && N <= 64 && KH == KW && (KH == 1 || KH == 3 || KH == 5 || KH == 7);
+// the problem of a forward entry point
+PatchProblem fwd_problem(PatchOp op, const float* bias, long ldx, int B, int H, int W, int Cin_p, int N, int KH, int KW, int accumulate = 0, int C2 = 0) {
+    return {op, B, H, W, Cin_p, N, KH, KW, ldx, accumulate != 0, ((uintptr_t)bias & 15) == 0, C2, 0, false};
 }
 
 }  // namespace
 
 #ifdef MTE_DEV
-extern "C" int mtei_set_patch_tall(int v) { if (v >= 700 && v < 710) { g_patch_m16_3 = v - 700; return MTE_OK; } if (v >= 600 && v < 610) { g_patch_m16_f1 = v - 600; return MTE_OK; } if (v >= 500 && v < 510) { g_patch_m16 = v - 500; return MTE_OK; } if (v >= 400 && v < 410) { g_patch_fwd2 = v - 400; return MTE_OK; } if (v >= 300 && v < 310) { g_patch_wgrad_wide = v - 300; return MTE_OK; } if (v >= 200 && v < 210) { g_patch_wgrad_8w = v - 200; return MTE_OK; } if (v >= 100) { g_patch_wgrad_wgs = v; return MTE_OK; } g_patch_tall = v; return MTE_OK; }
+extern "C" int mtei_set_patch_tall(int v) { return patch_knob_set(g_patch_knobs, v); }
 #endif
 
 extern "C" {
 
-// 1 if the LDS-patch kernels cover this conv shape (bf16, C_out <= 64, W % 32 == 0, k in {1,3,5,7}), else 0.
+// 1 if the LDS-patch kernels cover this conv shape (bf16, C_out <= 64, W % 32 == 0, k in {1,3,5,7}), else 0: what plan_patch says of a one-row forward
 int mte_conv2d_patch_supported(int W, int Cin_p, int N, int KH, int KW, int dtype) {
-    return (dtype == MTE_DT_BF16 && patch_shape_ok(W, Cin_p, N, KH, KW)) ? 1 : 0;
+    return (dtype == MTE_DT_BF16 && plan_patch(fwd_problem(PatchOp::Fwd, nullptr, Cin_p, 1, 1, W, Cin_p, N, KH, KW), g_patch_knobs).rc == MTE_OK) ? 1 : 0;
 }
 
 // 1 if mte_conv2d_patch_wgrad covers this shape: everything mte_conv2d_patch_supported covers, plus 3x3 layers with 65..128 output channels
 int mte_conv2d_patch_wgrad_supported(int W, int Cin_p, int N, int KH, int KW, int dtype) {
-    return (dtype == MTE_DT_BF16 && (patch_shape_ok(W, Cin_p, N, KH, KW) || patch_wgrad_wide_ok(W, Cin_p, N, KH, KW))) ? 1 : 0;
+    const PatchProblem p{PatchOp::Wgrad, 1, 1, W, Cin_p, N, KH, KW, Cin_p, false, true, 0, 1, false};
+    return (dtype == MTE_DT_BF16 && plan_patch(p, g_patch_knobs).rc == MTE_OK) ? 1 : 0;
 }
 
 // elements (bf16) of the fragment-block weight pack for mte_conv2d_patch_fwd
@@ -1276,26 +1202,24 @@ int mte_conv2d_patch_repack(const void* wgeneric, void* wpatch, int Cin_p, int N
 int mte_conv2d_patch_fwd(const void* x, long ldx, const void* wpatch, const float* bias, void* y, long ldy,
                          int B, int H, int W, int Cin_p, int N, int KH, int KW, int accumulate, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !wpatch || !y || !patch_shape_ok(W, Cin_p, N, KH, KW)) return MTE_ERR_ARG;
+    if (!x || !wpatch || !y) return MTE_ERR_ARG;
     PatchArgs a{(const bf16_t*)x, ldx, (const bf16_t*)wpatch, bias, (bf16_t*)y, ldy, B, H, W, Cin_p, N, accumulate ? 1 : 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0};
-    return N <= 32 ? dispatch_fwd<1>(a, KH, stream) : dispatch_fwd<2>(a, KH, stream);
+    return launch_patch_plan(plan_patch(fwd_problem(PatchOp::Fwd, bias, ldx, B, H, W, Cin_p, N, KH, KW, accumulate), g_patch_knobs), a, stream);
 }
 
-// mte_conv2d_patch_fwd that also leaves the GroupNorm(16) statistics of y as per-tile records (round 5): rec needs mte_conv2d_patch_fwd_gn_elems(B, H, W) floats;
-// *tiles_per_sample_out = records written per sample (the tile height depends on the kernel form), to be handed to mte_gn_stats_from_records.
-// With accumulate the records describe the SUMS this launch stores.  N % 16 == 0 (whole groups).
+// mte_conv2d_patch_fwd that also leaves the GroupNorm(16) statistics of y as per-tile records (round 5): rec needs mte_conv2d_patch_fwd_gn_elems(B, H, W) floats
+// (the 8-row tiles' count: an upper bound where 16-row tiles are chosen); *tiles_per_sample_out = records written per sample (the tile height depends on the
+// kernel form), to be handed to mte_gn_stats_from_records.  With accumulate the records describe the SUMS this launch stores.  N % 16 == 0 (whole groups).
 long mte_conv2d_patch_fwd_gn_elems(int B, int H, int W) { return (long)B * (W / TW) * ((H + TH - 1) / TH) * 32; }
 int mte_conv2d_patch_fwd_gn(const void* x, long ldx, const void* wpatch, const float* bias, void* y, long ldy, int B, int H, int W, int Cin_p, int N, int KH, int KW,
                             int accumulate, float* rec, long rec_elems, int* tiles_per_sample_out, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !wpatch || !y || !rec || !tiles_per_sample_out || !patch_shape_ok(W, Cin_p, N, KH, KW)) return MTE_ERR_ARG;
-    if (N % 16 != 0) return MTE_ERR_UNSUPPORTED;
-    if (rec_elems < mte_conv2d_patch_fwd_gn_elems(B, H, W)) return MTE_ERR_ARG;
+    if (!x || !wpatch || !y || !rec || !tiles_per_sample_out) return MTE_ERR_ARG;
+    const PatchPlan pl = plan_patch(fwd_problem(PatchOp::FwdGn, bias, ldx, B, H, W, Cin_p, N, KH, KW, accumulate), g_patch_knobs);
+    if (pl.rc == MTE_OK && rec_elems < mte_conv2d_patch_fwd_gn_elems(B, H, W)) return MTE_ERR_ARG;
     PatchArgs a{(const bf16_t*)x, ldx, (const bf16_t*)wpatch, bias, (bf16_t*)y, ldy, B, H, W, Cin_p, N, accumulate ? 1 : 0, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, rec};
-    int rows = TH;
-    const int rc = N <= 32 ? dispatch_fwd<1>(a, KH, stream, &rows) : dispatch_fwd<2>(a, KH, stream, &rows);
-    *tiles_per_sample_out = (W / TW) * ((H + rows - 1) / rows);
-    return rc;
+    if (pl.rc == MTE_OK) *tiles_per_sample_out = pl.tiles_per_sample;
+    return launch_patch_plan(pl, a, stream);
 }
 
 // The 3x3 forward with ONE MORE input channel given as a low-resolution map: y = conv_3(x, wpatch) + bias + conv_1(nearest_up2(inv), w1).  inv [B][H/2][W/2] fp32;
@@ -1303,72 +1227,35 @@ int mte_conv2d_patch_fwd_gn(const void* x, long ldx, const void* wpatch, const f
 // The term is formed in the store loop of the tile from LDS tables (the map under the tile + halo, the 9 x N weights): no pass over y before, no read of y.
 // _ok: 1 when this launch form exists for the shape (the caller otherwise writes the term with mte_rank1_conv_fwd and accumulates onto it).
 int mte_conv2d_patch_fwd_rank1_ok(const float* bias, long ldx, int B, int H, int W, int Cin_p, int N) {
-    if (!patch_shape_ok(W, Cin_p, N, 3, 3) || !g_patch_fwd2 || (H & 1) || (W & 1)) return 0;
-    if (N > 32 && Cin_p <= 64) return 0;                            // (those shapes run the first form of the kernel)
-    if ((((long)B * H * W - 1) * ldx + Cin_p) * 2 >= 0x7ff00000L || ((uintptr_t)bias & 15) != 0) return 0;
-    return 1;
+    return plan_patch(fwd_problem(PatchOp::FwdRank1, bias, ldx, B, H, W, Cin_p, N, 3, 3), g_patch_knobs).rc == MTE_OK ? 1 : 0;
 }
 int mte_conv2d_patch_fwd_rank1(const void* x, long ldx, const void* wpatch, const float* bias, void* y, long ldy, int B, int H, int W, int Cin_p, int N,
                                const float* inv, const float* w1, long w1_stride, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
     if (!x || !wpatch || !y || !inv || !w1) return MTE_ERR_ARG;
-    if (!mte_conv2d_patch_fwd_rank1_ok(bias, ldx, B, H, W, Cin_p, N)) return MTE_ERR_UNSUPPORTED;
     PatchArgs a{(const bf16_t*)x, ldx, (const bf16_t*)wpatch, bias, (bf16_t*)y, ldy, B, H, W, Cin_p, N, 0, inv, w1, w1_stride, nullptr, 0, nullptr, 0};
-    if (N <= 32) {
-        if (g_patch_tall && H >= 16) launch_form<true, 3, 1, true, true>(a, (long)(W / TW) * ((H + 15) / 16) * B, stream, g_patch_m16_3 != 0);
-        else launch_form<true, 3, 1, false, true>(a, (long)(W / TW) * ((H + TH - 1) / TH) * B, stream, g_patch_m16_3 != 0);
-    } else {
-        launch_form<true, 3, 2, false, true>(a, (long)(W / TW) * ((H + TH - 1) / TH) * B, stream, g_patch_m16_3 != 0);
-    }
-    return mte_check_launch();
+    return launch_patch_plan(plan_patch(fwd_problem(PatchOp::FwdRank1, bias, ldx, B, H, W, Cin_p, N, 3, 3), g_patch_knobs), a, stream);
 }
 
 // y = conv_3x3(x, wpatch) + conv_1x1(x2, wpatch2) + bias in ONE launch: the second term's C2 channels are further K-steps of every tile at the centre tap
 // (wpatch2: the fragment-block pack of the 1x1 weights for the same N).  Written for the data gradient of a residual block's input (reference layers01.py:55-73:
 // conv1 (3x3) and the 1x1 shortcut conv3 read the same x), dx = conv3x3^T(dy1) + conv1x1^T(dy3): instead of a 1x1 launch and an ACCUMULATING 3x3 launch.
-static int launch_plus1x1(const PatchArgs& a, hipStream_t stream, int* rows) {
-    const int B = a.B, H = a.H, W = a.W, N = a.N;
-    const bool v2 = g_patch_fwd2 && (N <= 32 || a.Cin_p > 64) && (((long)B * H * W - 1) * a.ldx + a.Cin_p) * 2 < 0x7ff00000L && ((uintptr_t)a.bias & 15) == 0;   // (as launch_fwd)
-    *rows = TH;
-    const bool m16 = v2 ? g_patch_m16_3 != 0 : g_patch_m16_f1 != 0;
-    if (N <= 32) {
-        if (g_patch_tall && H >= 16) {
-            *rows = 16;
-            const long tiles = (long)(W / TW) * ((H + 15) / 16) * B;
-            if (v2) launch_form<true, 3, 1, true, false, true>(a, tiles, stream, m16);
-            else launch_form<false, 3, 1, true, false, true>(a, tiles, stream, m16);
-        } else {
-            const long tiles = (long)(W / TW) * ((H + TH - 1) / TH) * B;
-            if (v2) launch_form<true, 3, 1, false, false, true>(a, tiles, stream, m16);
-            else launch_form<false, 3, 1, false, false, true>(a, tiles, stream, m16);
-        }
-    } else {
-        const long tiles = (long)(W / TW) * ((H + TH - 1) / TH) * B;
-        if (v2) launch_form<true, 3, 2, false, false, true>(a, tiles, stream, m16);
-        else launch_form<false, 3, 2, false, false, true>(a, tiles, stream, m16);
-    }
-    return mte_check_launch();
-}
 int mte_conv2d_patch_fwd_plus1x1(const void* x, long ldx, const void* wpatch, const float* bias, void* y, long ldy, int B, int H, int W, int Cin_p, int N,
                                  const void* x2, long ldx2, const void* wpatch2, int C2, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
-    if (!x || !wpatch || !y || !x2 || !wpatch2 || C2 < 8 || C2 % 8 != 0 || !patch_shape_ok(W, Cin_p, N, 3, 3)) return MTE_ERR_ARG;
+    if (!x || !wpatch || !y || !x2 || !wpatch2) return MTE_ERR_ARG;
     PatchArgs a{(const bf16_t*)x, ldx, (const bf16_t*)wpatch, bias, (bf16_t*)y, ldy, B, H, W, Cin_p, N, 0, nullptr, nullptr, 0, (const bf16_t*)x2, ldx2, (const bf16_t*)wpatch2, C2};
-    int rows;
-    return launch_plus1x1(a, stream, &rows);
+    return launch_patch_plan(plan_patch(fwd_problem(PatchOp::FwdPlus1x1, bias, ldx, B, H, W, Cin_p, N, 3, 3, 0, C2), g_patch_knobs), a, stream);
 }
-// dw_stage[N][KH*KW][Cin_p] fp32 (overwritten) for C_out <= 64; bf16 only.
+// dw_stage[N][KH*KW][Cin_p] fp32 (overwritten) for C_out <= 64, and for 3x3 layers with 65..128 output channels; bf16 only.  *parts_out: slabs written (1: dw_stage itself)
 int mte_conv2d_patch_wgrad(const void* x, long ldx, const void* dy, long lddy, float* dw_stage, int stage_parts, int* parts_out,
                            int B, int H, int W, int Cin_p, int N, int KH, int KW, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
     if (!x || !dy || !dw_stage) return MTE_ERR_ARG;
     PatchWgradArgs a{(const bf16_t*)x, ldx, (const bf16_t*)dy, lddy, dw_stage, B, H, W, Cin_p, N, 1};
-    if (parts_out) *parts_out = 1;
-    if (!patch_shape_ok(W, Cin_p, N, KH, KW)) {
-        if (!patch_wgrad_wide_ok(W, Cin_p, N, KH, KW)) return MTE_ERR_ARG;
-        return launch_wgrad_sl<3, 2, 2, 8, 2, 4>(a, stream, stage_parts, parts_out);
-    }
-    return N <= 32 ? dispatch_wgrad<1>(a, KH, stream, stage_parts, parts_out) : dispatch_wgrad<2>(a, KH, stream, stage_parts, parts_out);
+    const PatchPlan pl = plan_patch({PatchOp::Wgrad, B, H, W, Cin_p, N, KH, KW, ldx, false, true, 0, stage_parts, g_mte_wgrad_shared != 0}, g_patch_knobs);
+    if (parts_out) *parts_out = pl.parts_out;
+    return launch_patch_plan(pl, a, stream);
 }
 
 }  // extern "C"

@@ -206,7 +206,18 @@ class ModelWrapper(nn.Module):
             # inference has no optimizer step to poll the device error word (a GroupNorm cluster wait that gave up): one read of host memory, no
             # synchronisation -- a give-up of THIS forward surfaces at the latest at the next call (infer_edges.infer_depth waits and polls itself)
             from .. import kernels as K
-            K.check_device_errors()
+            from .._lib import MteError
+            try:
+                K.check_device_errors()
+            except MteError:
+                # the poll may see the first cluster kernel's report with later ones of the same forward still queued: they set the word again, and the
+                # NEXT forward would be blamed for it.  This one is lost anyway: wait for it and take its remaining reports with it
+                torch.cuda.synchronize()
+                try:
+                    K.check_device_errors()
+                except MteError:
+                    pass
+                raise
         return out
 
     def forward(self, *args, **kwargs):

@@ -5,10 +5,11 @@ into a line of text, and linked with tests/conv_launch_driver.cpp, which calls t
 the case (the driver's input line) and what was launched.  tests/test_conv_launch_table_cpu.py requires the working tree to reproduce every line.
 --gn: the same for norm_act.hip with tests/gn_launch_driver.cpp (four entry points, two queries, the clears) and tests/gn_launch_table.json
 (tests/test_gn_launch_table_cpu.py).  --p3: the same for pack3d.hip with tests/p3_launch_driver.cpp (the six conv3d pack / unpack entry points) and
-tests/p3_launch_table.json (tests/test_p3_launch_table_cpu.py).
+tests/p3_launch_table.json (tests/test_p3_launch_table_cpu.py).  --patch: the same for conv_patch.hip with tests/patch_launch_driver.cpp (the LDS-patch convolution's
+six launching entry points and its queries) and tests/patch_launch_table.json (tests/test_patch_launch_table_cpu.py).
 
-    python tests/conv_launch_recorder.py [--gn | --p3] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
-    python tests/conv_launch_recorder.py [--gn | --p3] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
 """
 import argparse
 import json
@@ -23,16 +24,17 @@ CSRC = os.path.join(ROOT, "mindtheedge_amd", "csrc")
 TABLE = os.path.join(TESTS, "conv_launch_table.json")
 GN_TABLE = os.path.join(TESTS, "gn_launch_table.json")
 P3_TABLE = os.path.join(TESTS, "p3_launch_table.json")
+PATCH_TABLE = os.path.join(TESTS, "patch_launch_table.json")
 HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
 BF16, F32 = 0, 1
 SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
 
 
-def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False):
+def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False):
     """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it;
-    p3: the conv3d pack / unpack driver and pack3d.hip)"""
-    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "") + ("recorder_dev" if dev else "recorder"))
+    p3: the conv3d pack / unpack driver and pack3d.hip; patch: the LDS-patch convolution driver and conv_patch.hip)"""
+    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "patch_" if patch else "") + ("recorder_dev" if dev else "recorder"))
     cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
     cmd += ["-DMTE_DEV"] if dev else []
     cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip")]
@@ -40,6 +42,8 @@ def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False):
         cmd += [os.path.join(csrc, "norm_act.hip"), os.path.join(TESTS, "gn_launch_driver.cpp")]
     elif p3:
         cmd += [os.path.join(csrc, "pack3d.hip"), os.path.join(TESTS, "p3_launch_driver.cpp")]
+    elif patch:
+        cmd += [os.path.join(csrc, "conv_patch.hip"), os.path.join(TESTS, "patch_launch_driver.cpp")]
     else:
         cmd += [os.path.join(TESTS, "conv_launch_driver.cpp")]
     cmd += ["-o", exe]
@@ -473,10 +477,220 @@ def p3_cases():
     return out
 
 
-def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False):
+# ---- LDS-patch convolution (--patch).  (cin, cout, k, B, H, W) of tests/test_gpu_conv_variants.py: SHAPES (those that reach the family) and PATCH_M16_SHAPES
+PATCH_T_SHAPES = [(32, 32, 7, 2, 16, 64), (512, 32, 5, 1, 12, 32), (3, 32, 5, 2, 20, 64), (65, 32, 3, 1, 9, 96), (64, 64, 3, 2, 16, 32), (32, 64, 1, 2, 8, 64),
+                  (97, 64, 3, 1, 24, 32), (1024, 64, 3, 1, 8, 32), (64, 32, 3, 2, 10, 32), (16, 16, 3, 1, 8, 32), (32, 64, 3, 1, 7, 64), (3, 32, 5, 1, 37, 96),
+                  (3, 16, 3, 2, 9, 32), (3, 32, 7, 1, 16, 32), (8, 24, 5, 2, 16, 64), (128, 128, 3, 2, 16, 64), (200, 128, 3, 1, 12, 32), (64, 128, 3, 2, 8, 64),
+                  (256, 128, 3, 1, 13, 32), (72, 96, 3, 2, 9, 32), (64, 72, 3, 1, 6, 96), (32, 32, 3, 1, 24, 64), (72, 32, 3, 1, 20, 32), (32, 32, 5, 1, 40, 64),
+                  (40, 32, 5, 1, 20, 32), (32, 24, 7, 1, 21, 32), (136, 64, 3, 1, 11, 64), (256, 64, 5, 1, 12, 64), (48, 56, 5, 2, 9, 32), (128, 32, 7, 1, 18, 32)]
+PATCH_T_M16 = [(32, 32, 7, 2, 16, 64), (128, 32, 7, 1, 18, 32), (256, 64, 5, 1, 12, 64), (48, 56, 5, 2, 9, 32), (64, 64, 3, 2, 16, 32), (32, 64, 1, 2, 8, 64),
+               (72, 32, 3, 1, 20, 32), (136, 64, 3, 1, 11, 64), (65, 32, 3, 1, 9, 96), (64, 32, 3, 2, 10, 32)]
+# tests/test_gpu_layers.py: (cm, cout, B, H, W) of the rank-1 test, (c1, cp, c2, B, H, W) of the plus-1x1 test
+PATCH_T_RANK1 = [(64, 32, 2, 32, 64), (64, 32, 1, 24, 32), (64, 32, 1, 8, 64), (96, 64, 2, 16, 64), (96, 64, 1, 20, 32), (32, 32, 1, 16, 32)]
+PATCH_T_PLUS = [(64, 64, 64, 2, 16, 64), (64, 32, 64, 1, 24, 32), (64, 32, 64, 2, 8, 32), (32, 64, 32, 1, 20, 64), (96, 64, 40, 1, 8, 32)]
+# tools/inloop_clock.py (cin, cout, k, H, W, pass, knob values), rank1_bench.py (cm, N, H, W), shortcut_fold_bench.py (c1, cp, c2, H, W); B = 8
+PATCH_TOOL_CLOCK = [(32, 32, 7, 384, 1280, "fwd", (500, 501)), (64, 32, 3, 192, 640, "fwd", ()), (64, 64, 3, 192, 640, "fwd", ()), (256, 64, 5, 96, 320, "fwd", (500, 501)),
+                    (64, 64, 3, 192, 640, "wgrad", ()), (32, 32, 7, 384, 1280, "wgrad", ())]
+PATCH_TOOL_RANK1 = [(64, 32, 384, 1280), (96, 64, 192, 640)]
+PATCH_TOOL_FOLD = [(64, 32, 64, 192, 640), (64, 64, 64, 192, 640)]
+PATCH_WGRAD_WGS, PATCH_WGRAD_WIDE_WGS = 192, 128      # MTE_PATCH_WGRAD_WGS, MTE_PATCH_WGRAD_WIDE_WGS (csrc/patch_plan.hpp)
+
+
+def patch_training_shapes():
+    """(entry, B, H, W, Cin_p, N, k) of every LDS-patch call of the T8 training step, bench.py's size (profiles/r06_v7_conv_table.txt)"""
+    seen = []
+    with open(os.path.join(ROOT, "profiles", "r06_v7_conv_table.txt")) as f:
+        for line in f:
+            m = re.search(r"mte_conv2d_patch_(\w+)\s+B,H,W,Cin_p,N,KH,KW=\((.*)\)", line)
+            if m:
+                key = (m.group(1).replace("fwd_rank1", "rank1").replace("fwd_plus1x1", "plus1x1"),) + tuple(int(v) for v in m.group(2).split(","))[:6]
+                if key not in seen:
+                    seen.append(key)
+    return seen
+
+
+def patch_wgrad_cap(cin_p, n, k, slabs=True):
+    """the slabs kernels.conv_wgrad makes room for"""
+    per = n * k * k * cin_p
+    wide = 256 if per <= (1 << 18) else (64 if per <= (1 << 19) else 32)
+    return max(1, min(512, (192 << 20) // (4 * per))) if slabs else max(1, min(wide, (96 << 20) // (4 * per)))
+
+
+def patch_wgrad_sl(cin_p, n, k):
+    """32-channel input slices a workgroup of the weight gradient takes, with the knobs at their defaults (plan_patch, csrc/patch_plan.hpp)"""
+    if k == 3 and n <= 64 and 64 < cin_p <= 96:
+        return 3
+    return 2 if n > 64 or (k <= 3 or k == 5 and n <= 32) and cin_p > 32 else 1
+
+
+def patch_case(entry, B, H, W, cin_p, N, kh, kw=None, ldx=None, acc=0, bias=0, C2=0, cap=0, shared=1, knobs=None):
+    """bias: -1 = none, else its offset from a 16-byte boundary; knobs: values of mte_debug_set(11, .), or (key, value) pairs"""
+    ks = ",".join("%d=%d" % (kv if isinstance(kv, tuple) else (11, kv)) for kv in knobs) if knobs else "-"
+    return "%s %d %d %d %d %d %d %d %d %d %d %d %d %d %s" % (entry, B, H, W, cin_p, N, kh, kh if kw is None else kw, cin_p if ldx is None else ldx, acc, bias, C2, cap,
+                                                             shared, ks)
+
+
+def patch_cases():
+    out = []
+
+    def add(*a, **kw):
+        c = patch_case(*a, **kw)
+        if c not in out:
+            out.append(c)
+
+    def layer(cin_p, n, k, B, H, W, knobs=None):
+        """what K.ConvFn runs for one layer: forward, data gradient (the transposed layer, no bias), weight gradient -- each only where the library's query
+        sends it to this family"""
+        add("fwd", B, H, W, cin_p, n, k, knobs=knobs)
+        add("fwd", B, H, W, n, cin_p, k, bias=-1, knobs=knobs)
+        add("wgrad", B, H, W, cin_p, n, k, cap=patch_wgrad_cap(cin_p, n, k), knobs=knobs)
+
+    # ---- the training step
+    for entry, B, H, W, cin_p, N, k in patch_training_shapes():
+        add("supported", B, H, W, cin_p, N, k)
+        add("wgrad_supported", B, H, W, cin_p, N, k)
+        if entry == "fwd":
+            for acc in (0, 1):
+                for bias in (0, -1):
+                    add("fwd", B, H, W, cin_p, N, k, acc=acc, bias=bias)
+        elif entry == "fwd_gn":
+            for acc in (0, 1):
+                add("fwd_gn", B, H, W, cin_p, N, k, acc=acc)
+            add("gn_elems", B, H, W, cin_p, N, k)
+        elif entry == "rank1":
+            add("rank1_ok", B, H, W, cin_p, N, k)
+            add("rank1", B, H, W, cin_p, N, k)
+        elif entry == "plus1x1":
+            for c2 in (32, 64):
+                add("plus1x1", B, H, W, cin_p, N, k, bias=-1, C2=c2)
+        else:
+            for shared in (1, 0):
+                for slabs in (True, False):
+                    add("wgrad", B, H, W, cin_p, N, k, cap=patch_wgrad_cap(cin_p, N, k, slabs), shared=shared)
+        if entry == "fwd":
+            add("repack", B, H, W, cin_p, N, k)
+            add("pack_elems", B, H, W, cin_p, N, k)
+
+    # ---- tests/test_gpu_conv_variants.py, tests/test_gpu_layers.py
+    for cin, cout, k, B, H, W in PATCH_T_SHAPES:
+        layer(round8(cin), cout, k, B, H, W)
+    for cin, cout, k, B, H, W in PATCH_T_M16:
+        layer(round8(cin), cout, k, B, H, W, knobs=[500, 600, 700])         # (the test's other half sets the defaults: the lines above)
+    for cm, cout, B, H, W in PATCH_T_RANK1:
+        add("rank1_ok", B, H, W, cm, cout, 3)
+        add("rank1", B, H, W, cm, cout, 3)
+        add("fwd", B, H, W, cm, cout, 3, acc=1)
+    for c1, cp, c2, B, H, W in PATCH_T_PLUS:
+        add("fwd", B, H, W, c2, cp, 1, bias=-1)
+        add("fwd", B, H, W, c1, cp, 3, acc=1, bias=-1)
+        add("plus1x1", B, H, W, c1, cp, 3, bias=-1, C2=c2)
+    # ---- tools/inloop_clock.py, rank1_bench.py, shortcut_fold_bench.py
+    for cin, cout, k, H, W, what, values in PATCH_TOOL_CLOCK:
+        for v in values or (None,):
+            add(what, 8, H, W, cin, cout, k, cap=patch_wgrad_cap(cin, cout, k) if what == "wgrad" else 0, knobs=v and [v])
+    for cm, N, H, W in PATCH_TOOL_RANK1:
+        add("rank1", 8, H, W, cm, N, 3)
+        add("fwd", 8, H, W, cm, N, 3, acc=1)
+    for c1, cp, c2, H, W in PATCH_TOOL_FOLD:
+        add("fwd", 8, H, W, c2, cp, 1, bias=-1)
+        add("fwd", 8, H, W, c1, cp, 3, acc=1, bias=-1)
+        add("plus1x1", 8, H, W, c1, cp, 3, bias=-1, C2=c2)
+
+    # ---- thresholds, one group at a time (B = 2, W = 64 unless the group is about them)
+    for cin_p in (8, 32, 40, 64, 72, 96, 104):                            # every class of Cin_p x N x K; every knob at 0 where it is asked
+        for n in (8, 32, 40, 64, 72, 128, 136):
+            if (cin_p == 8) != (n == 8) and not (cin_p == 8 and n == 32):
+                continue
+            for k in (1, 3, 5, 7):
+                if cin_p in (8, 32, 64):
+                    add("supported", 2, 24, 64, cin_p, n, k)
+                    for knobs in (None, [300]) if n > 64 and k == 3 else (None,):
+                        add("wgrad_supported", 2, 24, 64, cin_p, n, k, knobs=knobs)
+                if n <= 64:
+                    for knobs in (None, [400]) + (([0], [500], [600], [700]) if cin_p in (32, 72) else ()):
+                        add("fwd", 2, 24, 64, cin_p, n, k, knobs=knobs)
+                if n <= 64 or n <= 128 and k == 3:                         # (beyond: refused whatever the knobs, as the queries' lines say)
+                    for knobs in (None, [200]) + (([300],) if n > 64 else ()):
+                        add("wgrad", 2, 24, 64, cin_p, n, k, cap=64, knobs=knobs)
+            if n <= 64:
+                for entry, k0 in (("rank1_ok", ([400],)), ("rank1", ([0], [400], [700])), ("plus1x1", ([0], [400], [600], [700])), ("fwd_gn", ([0], [400]))):
+                    for knobs in (None,) + (k0 if cin_p in (32, 72) else k0[:1]):
+                        add(entry, 2, 24, 64, cin_p, n, 3, C2=32 if entry == "plus1x1" else 0, knobs=knobs)
+    for H in (15, 16):                                                     # tall tiles from 16 rows on (one output tile only); 14 / 16 for the rank-1 term, which wants H even
+        for cin_p, n, k in ((32, 32, 3), (32, 32, 5), (40, 32, 5), (40, 32, 3), (32, 64, 3), (72, 64, 3), (32, 32, 1), (32, 32, 7), (40, 32, 7)):
+            for acc in (0, 1):
+                add("fwd", 2, H, 64, cin_p, n, k, acc=acc)
+                add("fwd_gn", 2, H, 64, cin_p, n, k, acc=acc)
+            add("fwd", 2, H, 64, cin_p, n, k, knobs=[0])
+            add("wgrad", 2, H, 64, cin_p, n, k, cap=64)
+            if k == 3:
+                for h in (H, H - 1):
+                    add("rank1_ok", 2, h, 64, cin_p, n, 3)
+                    add("rank1", 2, h, 64, cin_p, n, 3)
+                add("plus1x1", 2, H, 64, cin_p, n, 3, C2=16)
+    for n in (16, 24, 40, 48):                                             # GroupNorm records want whole groups of N / 16 channels
+        add("fwd_gn", 2, 24, 64, 32, n, 3)
+    for kh, kw in ((2, 2), (4, 4), (3, 5), (3, 1), (9, 9)):          # even, mixed and other kernel sizes: refused
+        for entry in ("supported", "wgrad_supported", "fwd", "fwd_gn", "wgrad"):
+            for n in (32, 128) if "supported" in entry or entry == "wgrad" else (32,):
+                add(entry, 2, 24, 64, 64, n, kh, kw, cap=64)
+    for W in (32, 33, 48):                                             # W % 32
+        for entry in ("supported", "wgrad_supported", "fwd", "fwd_gn", "rank1_ok", "rank1", "plus1x1", "wgrad"):
+            add(entry, 2, 24, W, 64, 32, 3, C2=16, cap=64)
+        add("wgrad", 2, 24, W, 64, 128, 3, cap=64)
+    for cin_p, n in ((12, 32), (32, 12), (0, 32), (32, 0)):                # channel counts that are no multiple of 8, or none
+        for entry in ("supported", "wgrad_supported", "fwd", "wgrad"):
+            if "wgrad" not in entry or cin_p:                              # (no input channels, no slices to deal the groups over: the parent's query said yes and its launch divided by zero; now refused)
+                add(entry, 2, 24, 64, cin_p, n, 3, cap=64)
+    for B, H, W in ((0, 24, 64), (2, 0, 64), (2, 24, 0), (1, 1, 32)):      # empty tensors are refused nowhere: an empty grid
+        for entry in ("fwd", "fwd_gn", "gn_elems", "rank1", "plus1x1", "wgrad"):
+            add(entry, B, H, W, 32, 32, 3, C2=16, cap=64)
+    for c2 in (0, 4, 8, 12, 16, 72):                                       # channels of the 1x1 term
+        add("plus1x1", 2, 24, 64, 64, 32, 3, C2=c2)
+    for bias in (-1, 0, 4):                                            # the second form reads the bias in 16-byte groups
+        for entry, cin_p, n, k in (("fwd", 32, 32, 5), ("fwd", 72, 64, 3), ("fwd", 32, 64, 3), ("fwd_gn", 32, 32, 3), ("rank1_ok", 64, 32, 3), ("rank1", 64, 32, 3),
+                                   ("plus1x1", 64, 32, 3)):
+            add(entry, 2, 24, 64, cin_p, n, k, bias=bias, C2=16)
+    # one ldx on each side of the second form's 0x7ff00000-byte bound
+    for B, H, W, cin_p, n, k in ((8, 384, 1280, 32, 32, 7), (8, 192, 640, 96, 64, 3), (8, 192, 640, 64, 32, 3)):
+        edge = ((0x7ff00000 - 1) // 2 - cin_p) // (B * H * W - 1)
+        for ldx in (edge // 8 * 8, edge // 8 * 8 + 8):
+            for entry in ("fwd", "fwd_gn") + (("rank1_ok", "rank1", "plus1x1") if k == 3 else ()):
+                add(entry, B, H, W, cin_p, n, k, ldx=ldx, C2=16)
+            add("wgrad", B, H, W, cin_p, n, k, ldx=ldx, cap=512)
+    # the weight gradient's groups: want = wgs (x 2 alone on the chip) over the slices, capped by the tiles and by the slabs there is room for
+    for i, (cin_p, n, k) in enumerate(((64, 32, 3), (128, 128, 3), (96, 64, 3), (32, 32, 7), (256, 64, 5), (256, 32, 5))):
+        for shared in (1, 0):
+            for knobs in (None, [128], [384]) if i < 2 else (None,):
+                wgs = PATCH_WGRAD_WIDE_WGS if n > 64 else knobs[0] if knobs else PATCH_WGRAD_WGS
+                g = -(-wgs * (1 if shared else 2) // -(-cin_p // (32 * patch_wgrad_sl(cin_p, n, k))))
+                for cap in (0, 1, g - 1, g, g + 1):
+                    add("wgrad", 8, 192, 640, cin_p, n, k, cap=cap, shared=shared, knobs=knobs)
+        for B, H, W in ((1, 8, 32), (1, 9, 32), (2, 16, 64)):           # fewer tiles than groups
+            add("wgrad", B, H, W, cin_p, n, k, cap=512)
+    # the instances few calls reach: the first form where the second would be taken (a bias 4 bytes off a 16-byte boundary; knob 400), the 32x32x16 MFMA forms
+    # (500 / 600 / 700), each with and without accumulation, in 8-row and in 16-row tiles (one output tile only)
+    for k in (1, 3, 5, 7):
+        for n, H, cin_p in ((32, 8, 32), (32, 16, 32), (64, 8, 32), (64, 8, 72)):
+            if n == 64 and (k == 7 or cin_p == 72 and k != 3):
+                continue
+            for bias, knobs in ((4, None), (0, [500, 600, 700]), (0, [400, 600])):
+                for acc in (0, 1):
+                    add("fwd", 2, H, 64, cin_p, n, k, acc=acc, bias=bias, knobs=knobs)
+                if k == 3 and cin_p == 32:
+                    add("plus1x1", 2, H, 64, cin_p, n, 3, bias=bias, C2=16, knobs=knobs)
+            if k == 3:
+                add("rank1", 2, H, 64, cin_p, n, 3, knobs=[700])
+    # a knob soup and the reset: what mte_debug_set(33, 0) has to undo
+    for entry, cin_p, n, k in (("fwd", 32, 32, 5), ("wgrad", 96, 64, 3), ("plus1x1", 64, 32, 3)):
+        add(entry, 8, 192, 640, cin_p, n, k, C2=32, cap=512, knobs=[0, 128, 200, 300, 400, 500, 600, 700])
+    return out
+
+
+def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False, patch=False):
     with tempfile.TemporaryDirectory() as tmp:
-        cs = gn_cases() if gn else p3_cases() if p3 else cases()
-        return run(build(tmp, dev, csrc, extra, gn, p3), cs if dev else [c for c in cs if c.endswith(" -")])
+        cs = gn_cases() if gn else p3_cases() if p3 else patch_cases() if patch else cases()
+        return run(build(tmp, dev, csrc, extra, gn, p3, patch), cs if dev else [c for c in cs if c.endswith(" -")])
 
 
 def load_table(path=TABLE):
@@ -493,10 +707,11 @@ if __name__ == "__main__":
     ap.add_argument("--product", action="store_true", help="the build without -DMTE_DEV: the cases that set no knob")
     ap.add_argument("--gn", action="store_true", help="GroupNorm (norm_act.hip, tests/gn_launch_table.json)")
     ap.add_argument("--p3", action="store_true", help="conv3d pack / unpack (pack3d.hip, tests/p3_launch_table.json)")
+    ap.add_argument("--patch", action="store_true", help="LDS-patch convolution (conv_patch.hip, tests/patch_launch_table.json)")
     a = ap.parse_args()
-    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3)
+    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3, patch=a.patch)
     for ln in lines:
         json.loads(ln)
-    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else TABLE) if a.write else a.out, "w") as f:
+    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else PATCH_TABLE if a.patch else TABLE) if a.write else a.out, "w") as f:
         f.write("[\n" + ",\n".join(lines) + "\n]\n")
     print("%d cases" % len(lines))

@@ -1,7 +1,7 @@
 // Launch recorder for the host code that chooses kernels (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip /
-// norm_act.hip / pack3d.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
+// norm_act.hip / pack3d.hip / conv_patch.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
 // call reaches the HIP runtime: every launch is appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the
-// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args or P3LArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
+// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args, P3LArgs, PatchArgs or PatchWgradArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
 // kernels of mte_memset_async in common.hpp) is a line of its own: which buffer and how many bytes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -51,6 +51,10 @@ template <typename A, typename = void> struct is_p3_args : std::false_type {};  
 template <typename A> struct is_p3_args<A, std::void_t<decltype(A::dw3), decltype(A::db3), decltype(A::total)>> : std::true_type {};
 template <typename A, typename = void> struct is_p3l_args : std::false_type {};      // P3LArgs: every other conv3d kernel
 template <typename A> struct is_p3l_args<A, std::void_t<decltype(A::dwb), decltype(A::tiles_h), decltype(A::tshift)>> : std::true_type {};
+template <typename A, typename = void> struct is_patch_args : std::false_type {};    // PatchArgs: the LDS-patch forward kernels
+template <typename A> struct is_patch_args<A, std::void_t<decltype(A::r1_inv), decltype(A::x2), decltype(A::gn_rec)>> : std::true_type {};
+template <typename A, typename = void> struct is_patch_wgrad_args : std::false_type {};      // PatchWgradArgs
+template <typename A> struct is_patch_wgrad_args<A, std::void_t<decltype(A::lddy), decltype(A::groups), decltype(A::part_stride)>> : std::true_type {};
 
 // (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other fields 0, a pointer null)
 template <typename A> void arg_fields(const A& a) {
@@ -70,6 +74,12 @@ template <typename A> void arg_fields(const A& a) {
         field("dshift", a.dshift, 0); field("tshift", a.tshift, 0); field("ldx", a.ldx, 0); field("ldo", a.ldo, 0); field("lddst", a.lddst, 0);
         const std::string with = std::string(a.x ? " x" : "") + (a.o ? " o" : "") + (a.dst ? " dst" : "") + (a.w3 ? " w3" : "") + (a.b3 ? " b3" : "") + (a.dwb ? " dwb" : "");
         if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";
+    } else if constexpr (is_patch_args<A>::value) {
+        field("accum", a.accum, 0); field("C2", a.C2, 0); field("ldx", a.ldx, 0);
+        const std::string with = std::string(a.bias ? " bias" : "") + (a.r1_inv ? " r1_inv" : "") + (a.x2 ? " x2" : "") + (a.gn_rec ? " gn_rec" : "");
+        if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";
+    } else if constexpr (is_patch_wgrad_args<A>::value) {
+        field("groups", a.groups, 0); field("part_stride", a.part_stride, 0);
     }
 }
 

@@ -1,4 +1,4 @@
-// What the drivers of the launch recorder share (conv_launch_driver.cpp, gn_launch_driver.cpp, p3_launch_driver.cpp): the stand-ins for the rest of the library, the knob list of a
+// What the drivers of the launch recorder share (conv_launch_driver.cpp, gn_launch_driver.cpp, p3_launch_driver.cpp, patch_launch_driver.cpp): the stand-ins for the rest of the library, the knob list of a
 // case, and the loop that runs every case in a child process of its own.
 #pragma once
 #include <stdio.h>
@@ -15,7 +15,9 @@ int mte_debug_set(int key, int value);
 #ifndef MTE_REC_WITH_PACK3D                                                 // (the conv3d driver links pack3d.hip, which has the real one)
 int mtei_set_pack3d_lds(int) { return 0; }
 #endif
+#if !defined(MTE_REC_WITH_PATCH) || !defined(MTE_DEV)                      // (the LDS-patch driver links conv_patch.hip, whose development build has the real one)
 int mtei_set_patch_tall(int) { return 0; }
+#endif
 int mtei_set_tap_wgrad(int) { return 0; }
 int mtei_set_head_mfma(int) { return 0; }
 // A host-only object still registers its (absent) device code at start-up: answered here, so that this too stays out of the HIP runtime
