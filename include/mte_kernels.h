@@ -87,7 +87,8 @@ int mte_device_error_poll(void);
  * pixels is split over at most stage_parts workgroup groups; each one stores its PARTIAL gradient in its own part (plain stores;
  * *parts_out = parts written, mte_unpack_conv_wgrad adds them in part order: round 4 -- no floating-point atomics on the conv weight
  * gradient's path, the result does not depend on the order in which workgroups finish).  mte_unpack_conv_wgrad with parts > 32 uses
- * up to 32 further slabs BEHIND the parts as scratch: a stage of more than 32 parts is allocated with parts + 32 slabs. */
+ * up to 32 further slabs BEHIND the parts as scratch: a stage of more than 32 parts is allocated with parts + 32 slabs.
+ * MTE_ERR_ARG also for B, H, W, N, Cin_p, KH or KW below 1 and for a launch whose grid or block counts do not fit 32 bits. */
 int mte_conv2d_wgrad(const void* x, long ldx, const void* dy, long ldy, float* dw_stage, int stage_parts, int* parts_out,
                      int B, int H, int W, int Cin_p, int N, int KH, int KW, int dtype, mte_stream_t stream);
 /* 1 when mte_conv2d_wgrad takes this 3x3 bf16 layer with its nine-tap kernel (conv_wgrad9.hip: N % 128 == 0, Cin_p % 64 == 0, W % 32 == 0 or W % 16 == 0

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.hpp"
 #include "conv_plan.hpp"
+#include "wgrad_plan.hpp"
 
 struct ConvArgs {
     const void* x; long ldx;        // input pixels, elements per pixel (>= Cin_p)
@@ -35,3 +36,8 @@ struct ConvArgs {
 // conv_igemm8.hip: the 8-phase 256-row tile kernels (bf16, buffer-descriptor LDS-DMA).  Launches the instance the plan names (form P8_256x256 / P8_256x128,
 // kslice, one) with the plan's grid and LDS, after its LDS opt-in; decides nothing, the caller checks the launch.  a.splits / a.kslice are the plan's.
 __attribute__((visibility("hidden"))) int igemm8_launch(const IgemmPlan& p, const ConvArgs& a, hipStream_t st);
+
+// conv_wgrad9.hip: the nine-tap 3x3 weight gradient (bf16).  Launches conv_wgrad9_kernel<pl.rk> with the plan's tiles, K-steps, slab stride, grid and LDS, after
+// its LDS opt-in; decides nothing, the caller checks the launch.
+__attribute__((visibility("hidden"))) int wgrad9_launch(const WgradPlan& pl, const void* x, long ldx, const void* dy, long ldy, float* dw_stage,
+                                                        int B, int H, int W, int Cin_p, int N, hipStream_t st);

@@ -23,10 +23,6 @@
 #include "common.hpp"
 #include "conv_args.hpp"
 
-// conv_wgrad9.hip: the nine-tap 3x3 weight gradient (bf16).  MTE_ERR_UNSUPPORTED when the shape is outside what the kernel covers.
-__attribute__((visibility("hidden"))) int wgrad9_launch(const void* x, long ldx, const void* dy, long ldy, float* dw_stage, int parts_cap, int* parts_out,
-                                                        int B, int H, int W, int Cin_p, int N, hipStream_t st);
-
 // In-loop s_memtime sums of the DMA main loop (diagnostic build only: -DMTE_STAMPS, tools/igemm_stamps.py).  Round-3 reading, cycles per K-step
 // and wave: 256 x 128 tile (512 -> 512 @24x80) stage wait 57 | barrier 314 | DMA issue 267 | fragment reads + MFMA issue 468 | total 1192
 // (MFMA pipe busy 512); 256 x 256 tile (256 -> 256 @48x160) 68 | 861 | 207 | 484 | 1707 (pipe busy 1024).  Issuing the DMA behind the MFMAs
@@ -1243,124 +1239,55 @@ __global__ __launch_bounds__(WNO * WC * 64) void conv_wgrad_dma_kernel(WgradArgs
     }
 }
 
-int g_wgrad_dma = 1;                                 // development knob (mte_debug_set(4, v))
+WgradKnobs g_wgrad_knobs;                            // development knobs of plan_wgrad (wgrad_plan.hpp): mte_debug_set writes them, nothing else does
+static_assert(WG_RING == WGRAD_RING, "the plan sizes the LDS ring of conv_wgrad_dma_kernel");
 
-#ifndef MTE_WGRAD_WGS
-#define MTE_WGRAD_WGS 512
-#endif
-int g_wgrad_wgs = MTE_WGRAD_WGS;                     // development knob (mte_debug_set(9, v)): workgroups aimed for (pixel splits)
-int g_wgrad_big = 1;                                 // development knob (mte_debug_set(8, v)): 256 x 256 / 256 x 128 / 128 x 256 tiles
-                                                     // (4x fewer re-reads of dy / x; pays once the pixel splits are few: g_wgrad_wgs)
+// Compute units of the device, asked once per process: the nine-tap kernel's one-per-CU target and the LDS-DMA forms' whole-rounds search read it (WgradProblem::cus).
+// Where the query fails the plan is made for an MI355X: the count only steers how many pixel splits a launch gets, never what it computes.
+constexpr int WGRAD_CUS_FALLBACK = 256;
+int device_cus() {
+    static const int cus = [] {
+        int dev = 0, n = 0;
+        return hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : WGRAD_CUS_FALLBACK;
+    }();
+    return cus;
+}
 
-template <int WNO, int WC, int TNO, int TC>
-int launch_wgrad_dma(WgradArgs a, hipStream_t st, int parts_cap, int* parts_out) {
-    constexpr int BNO = WNO * TNO * 32, BC = WC * TC * 32, NTHR = WNO * WC * 64;
-    a.tiles_n = (a.N + BNO - 1) / BNO;
-    a.tiles_c = (a.Cin_p + BC - 1) / BC;
-    const int taps = a.KH * a.KW;
-    // row-aligned 32-pixel blocks waste MFMA work when W is not a multiple of 32 (W = 40: 37 %): use them for wide rows only
-    const bool fl = a.W % 32 == 0 || a.W >= 160;
-    const long nblk = fl ? (long)a.B * a.H * ((a.W + 31) / 32) : (a.M + 31) / 32;
-    const long base_wgs = (long)a.tiles_n * a.tiles_c * taps;
-    // ~4 workgroups of 256 threads (or 1 of 1024) per CU; three quarters of that beside the data-gradient chain (MTE_OPT_WGRAD_SHARES_CHIP; end of round 5,
-    // same box, ms per step: 512 -> 22.85, 384 -> 22.70, 256 -> 22.79, 768 -> 22.77 -- profiles/r05_side_queue_width.txt)
-    const long want = (long)(g_mte_wgrad_shared ? g_wgrad_wgs * 3 / 4 : g_wgrad_wgs) * 256 / NTHR;
-    long splits = (want + base_wgs - 1) / base_wgs;
-    const long max_splits = (nblk + 15) / 16;                   // at least 16 pixel blocks per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    if (!g_mte_wgrad_shared) {
-        // alone on the chip the launch runs in whole rounds of (CUs x workgroups per CU): 50 tiles x 6 splits = 300 one-per-CU workgroups took two rounds, the second
-        // 17 % full (5x5 512 -> 128 @48x160: 0.366 ms at 550 TFLOP/s; 5 splits = 250 workgroups: one round).  Among the split counts around the one above take the
-        // cheapest in rounds per split; ties go to fewer partial slabs.
-        static int cus = 0;
-        if (!cus) { int dev = 0; if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256; }
-        const size_t lds_wg = (size_t)WG_RING * 32 * (BNO + BC) * 2;
-        long per_cu = (long)(160 * 1024 / lds_wg);
-        if (per_cu > 2048 / NTHR) per_cu = 2048 / NTHR;
-        if (per_cu < 1) per_cu = 1;
-        const long slots = per_cu * cus;
-        long best = splits; double best_cost = 1e30;
-        for (long sc = splits > 2 ? splits - 2 : 1; sc <= splits + 2 && sc <= max_splits && sc <= (parts_cap < 1 ? 1 : parts_cap); ++sc) {
-            const double cost = (double)((base_wgs * sc + slots - 1) / slots) / (double)sc;
-            if (cost < best_cost * 0.98) { best_cost = cost; best = sc; }
-        }
-        splits = best;
+// The one launch path of mte_conv2d_wgrad: *parts_out, the clear and the launch the plan names (the nine-tap pair behind its LDS opt-in: wgrad9_launch).  Decides nothing.
+#define WGRAD_FL(KERNEL, ...) \
+    if (pl.row_aligned) hipLaunchKernelGGL((KERNEL<__VA_ARGS__, true>), grid, block, pl.lds, st, a); \
+    else hipLaunchKernelGGL((KERNEL<__VA_ARGS__, false>), grid, block, pl.lds, st, a); \
+    break;
+#define WGRAD_DMA(WNO, WC, TNO, TC) case wgrad_key(WgradFamily::Dma, 2, WNO, WC, TNO, TC): WGRAD_FL(conv_wgrad_dma_kernel, WNO, WC, TNO, TC)
+#define WGRAD_REG(WNO, WC, TNO, TC) \
+    case wgrad_key(WgradFamily::Reg, 2, WNO, WC, TNO, TC): WGRAD_FL(conv_wgrad_kernel, bf16_t, WNO, WC, TNO, TC) \
+    case wgrad_key(WgradFamily::Reg, 4, WNO, WC, TNO, TC): WGRAD_FL(conv_wgrad_kernel, float, WNO, WC, TNO, TC)
+int launch_wgrad_plan(const WgradPlan& pl, int elem_size, WgradArgs a, int* parts_out, hipStream_t st) {
+    if (parts_out) *parts_out = pl.parts_out;
+    if (pl.clear_bytes && mte_memset_async(a.dw, 0, pl.clear_bytes, st) != hipSuccess) return MTE_ERR_LAUNCH;
+    a.tiles_n = pl.tiles_n; a.tiles_c = pl.tiles_c; a.splits = pl.splits; a.blocks_per_split = pl.blocks_per_split; a.part_stride = pl.part_stride;
+    const dim3 grid(pl.grid), block((unsigned)pl.threads);
+    switch (wgrad_key(pl, elem_size)) {
+    case wgrad_key(WgradFamily::NineTap, 2, 1, 0, 0, 0):
+    case wgrad_key(WgradFamily::NineTap, 2, 2, 0, 0, 0):
+        if (wgrad9_launch(pl, a.x, a.ldx, a.dy, a.ldy, a.dw, a.B, a.H, a.W, a.Cin_p, a.N, st) != MTE_OK) return MTE_ERR_LAUNCH;
+        break;
+    WGRAD_DMA(4, 4, 2, 2)        // 256 x 256, 16 waves
+    WGRAD_DMA(4, 2, 2, 2)        // 256 x 128, 8 waves
+    WGRAD_DMA(2, 4, 2, 2)        // 128 x 256, 8 waves
+    WGRAD_DMA(2, 2, 1, 2)        // 64 x 128
+    WGRAD_DMA(2, 2, 2, 2)        // 128 x 128
+    WGRAD_REG(1, 4, 1, 1)        // 32 x 128
+    WGRAD_REG(2, 2, 1, 2)        // 64 x 128
+    WGRAD_REG(2, 2, 2, 2)        // 128 x 128
+    default: return MTE_ERR_UNSUPPORTED;
     }
-    // one partial gradient per pixel split (plain stores, summed in part order by the unpack pass): never more splits than the caller's stage
-    // has parts -- round 4: the fp32-atomic combine that used to take over beyond stage_parts is gone from this kernel's launch path, the
-    // weight gradient is a fixed-order sum (the atomics cost 0.4 ms per step when they were the default, and made the result order-dependent)
-    if (splits > parts_cap) splits = parts_cap < 1 ? 1 : parts_cap;
-    a.blocks_per_split = (int)((nblk + splits - 1) / splits);
-    a.splits = (int)((nblk + a.blocks_per_split - 1) / a.blocks_per_split);
-    if (a.splits > 1 && a.splits <= parts_cap) {
-        a.part_stride = (long)a.N * taps * a.Cin_p;
-        if (parts_out) *parts_out = a.splits;
-    } else {
-        a.part_stride = 0;
-        if (parts_out) *parts_out = 1;
-        if (a.splits > 1 && mte_memset_async(a.dw, 0, sizeof(float) * (size_t)a.N * taps * a.Cin_p, st) != hipSuccess) return MTE_ERR_LAUNCH;
-    }
-    const size_t lds = WG_RING * 32 * (BNO + BC) * 2;
-    const dim3 grid((unsigned)(base_wgs * a.splits));
-    if (fl) hipLaunchKernelGGL((conv_wgrad_dma_kernel<WNO, WC, TNO, TC, true>), grid, dim3(NTHR), lds, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_dma_kernel<WNO, WC, TNO, TC, false>), grid, dim3(NTHR), lds, st, a);
     return mte_check_launch();
 }
+#undef WGRAD_REG
+#undef WGRAD_DMA
+#undef WGRAD_FL
 
-template <typename T, int WNO, int WC, int TNO, int TC>
-int launch_wgrad(WgradArgs a, hipStream_t st) {
-    constexpr int BNO = WNO * TNO * 32, BC = WC * TC * 32, ES = (int)sizeof(T);
-    constexpr int RS_Y = (BNO * ES % 128 == 64) ? BNO * ES : BNO * ES + 64;
-    constexpr int RS_X = (BC * ES % 128 == 64) ? BC * ES : BC * ES + 64;
-    a.tiles_n = (a.N + BNO - 1) / BNO;
-    a.tiles_c = (a.Cin_p + BC - 1) / BC;
-    const int taps = a.KH * a.KW;
-    const long es = (long)sizeof(T);
-    // row-aligned 32-pixel blocks waste MFMA work when W is not a multiple of 32 (W = 40: 37 %): use them for wide rows only
-    const bool fl = (a.W % 32 == 0 || a.W >= 160) &&
-                    ((a.M + a.KW) * a.ldx + a.Cin_p) * es < 0x7ff00000L && ((a.M - 1) * a.ldy + a.N) * es < 0x7ff00000L;
-    const long nblk = fl ? (long)a.B * a.H * ((a.W + 31) / 32) : (a.M + 31) / 32;
-    const long base_wgs = (long)a.tiles_n * a.tiles_c * taps;
-    long splits = (1024 + base_wgs - 1) / base_wgs;            // aim for >= ~4 workgroups per CU
-    const long max_splits = (nblk + 15) / 16;                   // at least 16 pixel blocks per workgroup
-    if (splits > max_splits) splits = max_splits;
-    if (splits < 1) splits = 1;
-    a.blocks_per_split = (int)((nblk + splits - 1) / splits);
-    a.splits = (int)((nblk + a.blocks_per_split - 1) / a.blocks_per_split);
-    if (a.splits > 1) {
-        hipError_t e = mte_memset_async(a.dw, 0, sizeof(float) * (size_t)a.N * taps * a.Cin_p, st);
-        if (e != hipSuccess) return MTE_ERR_LAUNCH;
-    }
-    const size_t lds = 2 * 32 * (RS_Y + RS_X);
-    if (fl) hipLaunchKernelGGL((conv_wgrad_kernel<T, WNO, WC, TNO, TC, true>), dim3((unsigned)(base_wgs * a.splits)), dim3(256), lds, st, a);
-    else hipLaunchKernelGGL((conv_wgrad_kernel<T, WNO, WC, TNO, TC, false>), dim3((unsigned)(base_wgs * a.splits)), dim3(256), lds, st, a);
-    return mte_check_launch();
-}
-
-template <typename T> int dispatch_wgrad(const WgradArgs& a, hipStream_t st, int parts_cap, int* parts_out) {
-    if (parts_out) *parts_out = 1;
-    if constexpr (sizeof(T) == 2) {
-        const bool fits = ((a.M + a.KW) * a.ldx + a.Cin_p) * 2 < 0x7ff00000L && ((a.M - 1) * a.ldy + a.N) * 2 < 0x7ff00000L;
-        if (g_wgrad_dma && fits && a.N > 32 && a.Cin_p > 32)
-        {
-            // (round 4, measured and NOT adopted: 8 waves of 128 x 64 on the same tile -- 1.5 transposing reads per MFMA instead of 2 -- run 20-30 % slower
-            //  than the 16-wave form on every 256-multiple layer, 256 -> 256 @48x160 167 vs 130 us with the unpack pass: with one barrier per
-            //  32-pixel step the loop needs its four waves per SIMD; development knob 8 = 3 selects it)
-            if (g_wgrad_big == 3 && a.N % 256 == 0 && a.Cin_p % 256 == 0) return launch_wgrad_dma<2, 4, 4, 2>(a, st, parts_cap, parts_out);   // 256 x 256, 8 waves
-            if (g_wgrad_big && a.N % 256 == 0 && a.Cin_p % 256 == 0) return launch_wgrad_dma<4, 4, 2, 2>(a, st, parts_cap, parts_out);   // 256 x 256, 16 waves
-            if (g_wgrad_big && a.N % 256 == 0 && a.Cin_p >= 128) return launch_wgrad_dma<4, 2, 2, 2>(a, st, parts_cap, parts_out);     // 256 x 128, 8 waves
-            if (g_wgrad_big && a.N >= 128 && a.Cin_p % 256 == 0) return launch_wgrad_dma<2, 4, 2, 2>(a, st, parts_cap, parts_out);     // 128 x 256, 8 waves
-            return a.N <= 64 ? launch_wgrad_dma<2, 2, 1, 2>(a, st, parts_cap, parts_out) : launch_wgrad_dma<2, 2, 2, 2>(a, st, parts_cap, parts_out);
-        }
-    }
-    if (a.N <= 32) {
-        if (a.Cin_p <= 32) return launch_wgrad<T, 1, 4, 1, 1>(a, st);      // 32 x 128 would waste: 32 x (4*32)
-        return launch_wgrad<T, 1, 4, 1, 1>(a, st);                          // cout 32 x cin 128
-    }
-    if (a.N <= 64) return launch_wgrad<T, 2, 2, 1, 2>(a, st);              // cout 64 x cin 128
-    return launch_wgrad<T, 2, 2, 2, 2>(a, st);                              // cout 128 x cin 128
-}
 
 // ---- weight packing: OIHW fp32 master -> [N][taps][Cin_p] (forward) and [Cin_p8][taps flipped][Cout_p] (dgrad).
 // Both passes go through LDS so that global reads AND writes are contiguous runs (the naive gather read the fp32
@@ -1632,19 +1559,14 @@ extern "C" int mtei_set_gn(int key, int value);
 extern "C" int mtei_set_patch_tall(int v);           // PatchKnobs (patch_plan.hpp)
 extern "C" int mtei_set_tap_wgrad(int v);            // tap_wgrad.hip
 extern "C" int mtei_set_head_mfma(int v);
-extern int g_wgrad9, g_wgrad9_wgs;
 int mte_debug_set(int key, int value) {
     if (key == MTE_KNOB_IGEMM_RESET) { (void)mtei_set_pack3d_lds(-1); (void)mtei_set_patch_tall(-1); }   // 33 also puts the conv3d pack / unpack and the LDS-patch knobs back (P3_KNOB_RESET, PATCH_KNOB_RESET)
-    if (igemm_knob_set(g_igemm_knobs, key, value)) return MTE_OK;      // keys 0, 6, 7, 15, 17, 19, 21, 23, 24, 28, 29, 32; 33 = all of them back to their defaults
-    if (key == 26) { g_wgrad9 = value; return MTE_OK; }
-    if (key == 27) { g_wgrad9_wgs = value; return MTE_OK; }
+    const bool wgrad = wgrad_knob_set(g_wgrad_knobs, key, value);      // keys 4, 8, 9, 26, 27 (WgradKnobs, wgrad_plan.hpp); 33 = all of them back to their defaults too
+    if (igemm_knob_set(g_igemm_knobs, key, value) || wgrad) return MTE_OK;      // keys 0, 6, 7, 15, 17, 19, 21, 23, 24, 28, 29, 32; 33 = all of them back to their defaults
     if (key == 30) return mtei_set_head_mfma(value);
     if (key == 31) return mtei_set_tap_wgrad(value);
     if (key == 1) return mtei_set_pack3d_lds(value);
     if (key == 2 || key == 3 || key == 13 || key == 14 || key == 25) return mtei_set_gn(key, value);      // GnKnobs (gn_plan.hpp)
-    if (key == 4) { g_wgrad_dma = value; return MTE_OK; }
-    if (key == 8) { g_wgrad_big = value; return MTE_OK; }
-    if (key == 9) { g_wgrad_wgs = value; return MTE_OK; }
     if (key == 11) return mtei_set_patch_tall(value);
     return MTE_ERR_ARG;
 }
@@ -1695,21 +1617,20 @@ int mte_conv2d_igemm_sparse(const void* x, long ldx, const void* wpack, const fl
     return plan_and_launch(a, dtype == MTE_DT_BF16 ? 2 : 4, 0, stream);
 }
 
-// dw_stage[N][KH*KW][Cin_p] (fp32) = sum over pixels of dy (x) shifted x.
+// dw_stage[N][KH*KW][Cin_p] (fp32) = sum over pixels of dy (x) shifted x.  Which kernel, how many pixel splits and slabs: plan_wgrad (wgrad_plan.hpp).
 int mte_conv2d_wgrad(const void* x, long ldx, const void* dy, long ldy, float* dw_stage, int stage_parts, int* parts_out,
                      int B, int H, int W, int Cin_p, int N, int KH, int KW, int dtype, hipStream_t stream) {
     (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
     if (!x || !dy || !dw_stage) return MTE_ERR_ARG;
-    if (Cin_p % 8 != 0 || N % 8 != 0) return MTE_ERR_ARG;
-    WgradArgs a{x, ldx, dy, ldy, dw_stage, B, H, W, Cin_p, N, KH, KW, (long)B * H * W, 1, 0, 0, 0};
-    if (dtype == MTE_DT_BF16 && KH == 3 && KW == 3 && stage_parts >= 1 && parts_out) {
-        // round 5: the 3x3 layers with >= 64 / 128 channels take all nine taps from one staged patch (conv_wgrad9.hip)
-        const int rc = wgrad9_launch(x, ldx, dy, ldy, dw_stage, stage_parts, parts_out, B, H, W, Cin_p, N, stream);
-        if (rc != MTE_ERR_UNSUPPORTED) return rc;
-    }
-    if (dtype == MTE_DT_BF16) return dispatch_wgrad<bf16_t>(a, stream, stage_parts, parts_out);
-    if (dtype == MTE_DT_F32) return dispatch_wgrad<float>(a, stream, stage_parts, parts_out);
-    return MTE_ERR_UNSUPPORTED;
+    const int es = dtype == MTE_DT_BF16 ? 2 : dtype == MTE_DT_F32 ? 4 : 0;
+    const WgradPlan pl = plan_wgrad({es, B, H, W, Cin_p, N, KH, KW, ldx, ldy, stage_parts, parts_out != nullptr, g_mte_wgrad_shared != 0, device_cus()}, g_wgrad_knobs);
+    if (pl.rc != MTE_OK) return pl.rc;         // (before the pixel count is formed: the plan has refused what does not fit)
+    return launch_wgrad_plan(pl, es, WgradArgs{x, ldx, dy, ldy, dw_stage, B, H, W, Cin_p, N, KH, KW, (long)B * H * W, 1, 0, 0, 0}, parts_out, stream);
+}
+
+// 1: mte_conv2d_wgrad takes the nine-tap kernel for this layer (given a stage of at least one slab, parts_out and operands inside a buffer descriptor)
+int mte_conv2d_wgrad_nine_tap(int H, int W, int Cin_p, int N, int KH, int KW, int dtype) {
+    return wgrad_nine_tap_rk(g_wgrad_knobs, dtype == MTE_DT_BF16 ? 2 : 0, H, W, Cin_p, N, KH, KW) ? 1 : 0;
 }
 
 int mte_pack_conv_weights(const float* w_oihw, void* wfwd, void* wbwd, int Cout, int Cin, int KH, int KW,

@@ -27,6 +27,7 @@
 //   * operands swapped (D = X^T dY): a lane ends with 4 consecutive INPUT channels of one output channel = one 16-byte store into the
 //     [N][9][Cin_p] staging slab of its pixel split (plain stores; mte_unpack_conv_wgrad adds the slabs in order: no atomics, bit-reproducible).
 #include "common.hpp"
+#include "conv_args.hpp"
 #include <type_traits>
 
 // Private diagnostic builds (tools/w9_ablate.py; the shipped library defines none of this): leave out pieces of the main loop to see what a K-step
@@ -290,65 +291,16 @@ __global__ __launch_bounds__(512, 2) void conv_wgrad9_kernel(Wgrad9Args a) {
         }
 }
 
-int g_cus9 = 0;
-
 }  // namespace
 
-int g_wgrad9 = 1;                                    // development knob (mte_debug_set(26, v)): 0 = the generic per-tap kernel everywhere
-// Workgroups aimed for per launch when the caller runs the weight gradients BESIDE the data-gradient chain (MTE_OPT_WGRAD_SHARES_CHIP): HALF the chip.
-// With one workgroup per CU this kernel's 96 KB of LDS, 512 threads and whole register file take every CU away from the main queue's kernels for its whole length
-// and it writes twice the slabs (what the main queue loses is less the CUs than the clock: profiles/r05_overlap_probe.txt).  Same-box step times (profiles/r05_side_queue_width.txt): 256 -> 23.59 ms, 192 -> 23.50, 128 -> 23.26, 96 -> 23.35, 64 -> 23.79.
-// Alone on the chip (option off: serial profiling runs, a binding without a second stream) it takes one workgroup per CU.
-#ifndef MTE_W9_WGS
-#define MTE_W9_WGS 128
-#endif
-int g_wgrad9_wgs = MTE_W9_WGS;                       // development knob (mte_debug_set(27, v)): workgroups aimed for per shared-chip launch (0 = one per CU)
-
-static int wgrad9_form(int H, int W, int Cin_p, int N) {     // 0: not this kernel's; 1: 1 x 32 K-steps; 2: 2 x 16
-    if (!g_wgrad9 || N % 128 != 0 || Cin_p % 64 != 0) return 0;
-    // 1 x 32 K-steps where the rows allow it: measured 2-4 % faster on the 48x160 layers than 2 x 16 ones although they stage 15 patch pieces against 12
-    // (development knob 26 = 2: 2 x 16 first)
-    const bool ok2 = W % 16 == 0 && H % 2 == 0, ok1 = W % 32 == 0;
-    return g_wgrad9 == 2 ? (ok2 ? 2 : (ok1 ? 1 : 0)) : (ok1 ? 1 : (ok2 ? 2 : 0));
-}
-extern "C" int mte_conv2d_wgrad_nine_tap(int H, int W, int Cin_p, int N, int KH, int KW, int dtype) {
-    return dtype == MTE_DT_BF16 && KH == 3 && KW == 3 && H > 0 && W > 0 && wgrad9_form(H, W, Cin_p, N) ? 1 : 0;
-}
-
-// -> MTE_OK and *parts_out slabs written, or MTE_ERR_UNSUPPORTED (the caller takes the generic kernel)
-__attribute__((visibility("hidden"))) int wgrad9_launch(const void* x, long ldx, const void* dy, long ldy, float* dw_stage, int parts_cap, int* parts_out,
-                                                        int B, int H, int W, int Cin_p, int N, hipStream_t st) {
-    if (parts_cap < 1) return MTE_ERR_UNSUPPORTED;
-    const int rk = wgrad9_form(H, W, Cin_p, N);
-    if (!rk) return MTE_ERR_UNSUPPORTED;
-    const long M = (long)B * H * W;
-    if (((M + 2 * W + 16) * ldx) * 2 >= 0x7ff00000L || ((M - 1) * ldy + N) * 2 >= 0x7ff00000L) return MTE_ERR_UNSUPPORTED;
-    if (!g_cus9) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) return MTE_ERR_LAUNCH;
-        g_cus9 = n;
-    }
+// The instance, tiles, K-steps per split, slab stride, grid and LDS are the plan's (plan_wgrad, wgrad_plan.hpp); the caller checks the launch
+int wgrad9_launch(const WgradPlan& pl, const void* x, long ldx, const void* dy, long ldy, float* dw_stage, int B, int H, int W, int Cin_p, int N, hipStream_t st) {
     Wgrad9Args a{};
-    a.x = (const bf16_t*)x; a.ldx = ldx; a.dy = (const bf16_t*)dy; a.ldy = ldy; a.dw = dw_stage;
+    a.x = (const bf16_t*)x; a.ldx = ldx; a.dy = (const bf16_t*)dy; a.ldy = ldy; a.dw = dw_stage; a.part_stride = pl.part_stride;
     a.B = B; a.H = H; a.W = W; a.Cin_p = Cin_p; a.N = N;
-    a.tiles_c = Cin_p / 64;
-    a.base = (N / 128) * a.tiles_c;
-    a.units = (int)(M / 32);
-    // one workgroup per CU (96 KB of LDS, 512 threads): pixel splits so that tiles x splits ~ the CU count, at least 12 K-steps each
-    const int target = (g_mte_wgrad_shared && g_wgrad9_wgs > 0) ? g_wgrad9_wgs : g_cus9;
-    long splits = (target + a.base / 2) / a.base;
-    if (splits < 1) splits = 1;
-    if (splits > parts_cap) splits = parts_cap;
-    if (splits > a.units / 12) splits = a.units / 12 > 0 ? a.units / 12 : 1;
-    a.units_per_split = (int)((a.units + splits - 1) / splits);
-    a.units_per_split = (a.units_per_split + 3) & ~3;  // the main loop is unrolled over its four ring slots
-    splits = (a.units + a.units_per_split - 1) / a.units_per_split;
-    a.part_stride = (long)N * 9 * Cin_p;
-    if (parts_out) *parts_out = (int)splits;
-    constexpr int LDS = 4 * (8 + 16) * 1024;
-    if (mte_allow_lds<conv_wgrad9_kernel<1>>(LDS) != MTE_OK || mte_allow_lds<conv_wgrad9_kernel<2>>(LDS) != MTE_OK) return MTE_ERR_LAUNCH;
-    const dim3 grid((unsigned)(a.base * splits));
-    if (rk == 1) hipLaunchKernelGGL(conv_wgrad9_kernel<1>, grid, dim3(512), LDS, st, a);
-    else hipLaunchKernelGGL(conv_wgrad9_kernel<2>, grid, dim3(512), LDS, st, a);
-    return mte_check_launch();
+    a.tiles_c = pl.tiles_c; a.base = pl.base; a.units = pl.units; a.units_per_split = pl.units_per_split;
+    if (pl.lds_optin && (pl.rk == 1 ? mte_allow_lds<conv_wgrad9_kernel<1>>((int)pl.lds) : mte_allow_lds<conv_wgrad9_kernel<2>>((int)pl.lds)) != MTE_OK) return MTE_ERR_LAUNCH;
+    if (pl.rk == 1) hipLaunchKernelGGL(conv_wgrad9_kernel<1>, dim3(pl.grid), dim3((unsigned)pl.threads), pl.lds, st, a);
+    else hipLaunchKernelGGL(conv_wgrad9_kernel<2>, dim3(pl.grid), dim3((unsigned)pl.threads), pl.lds, st, a);
+    return MTE_OK;
 }

@@ -6,10 +6,12 @@ the case (the driver's input line) and what was launched.  tests/test_conv_launc
 --gn: the same for norm_act.hip with tests/gn_launch_driver.cpp (four entry points, two queries, the clears) and tests/gn_launch_table.json
 (tests/test_gn_launch_table_cpu.py).  --p3: the same for pack3d.hip with tests/p3_launch_driver.cpp (the six conv3d pack / unpack entry points) and
 tests/p3_launch_table.json (tests/test_p3_launch_table_cpu.py).  --patch: the same for conv_patch.hip with tests/patch_launch_driver.cpp (the LDS-patch convolution's
-six launching entry points and its queries) and tests/patch_launch_table.json (tests/test_patch_launch_table_cpu.py).
+six launching entry points and its queries) and tests/patch_launch_table.json (tests/test_patch_launch_table_cpu.py).  --wgrad: the same for mte_conv2d_wgrad and its
+query (conv_igemm.hip, conv_wgrad9.hip) with tests/wgrad_launch_driver.cpp and tests/wgrad_launch_table.json (tests/test_wgrad_launch_table_cpu.py); the shim answers
+the device query with the CU count of the case.
 
-    python tests/conv_launch_recorder.py [--gn | --p3 | --patch] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
-    python tests/conv_launch_recorder.py [--gn | --p3 | --patch] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
 """
 import argparse
 import json
@@ -25,25 +27,29 @@ TABLE = os.path.join(TESTS, "conv_launch_table.json")
 GN_TABLE = os.path.join(TESTS, "gn_launch_table.json")
 P3_TABLE = os.path.join(TESTS, "p3_launch_table.json")
 PATCH_TABLE = os.path.join(TESTS, "patch_launch_table.json")
+WGRAD_TABLE = os.path.join(TESTS, "wgrad_launch_table.json")
 HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
 BF16, F32 = 0, 1
 SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
 
 
-def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False):
+def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False, wgrad=False):
     """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it;
-    p3: the conv3d pack / unpack driver and pack3d.hip; patch: the LDS-patch convolution driver and conv_patch.hip)"""
-    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "patch_" if patch else "") + ("recorder_dev" if dev else "recorder"))
+    p3: the conv3d pack / unpack driver and pack3d.hip; patch: the LDS-patch convolution driver and conv_patch.hip; wgrad: the weight-gradient driver.
+    conv_wgrad9.hip is linked into all of them: conv_igemm.hip launches through it)"""
+    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "patch_" if patch else "wgrad_" if wgrad else "") + ("recorder_dev" if dev else "recorder"))
     cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
     cmd += ["-DMTE_DEV"] if dev else []
-    cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip")]
+    cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip"), os.path.join(csrc, "conv_wgrad9.hip")]
     if gn:
         cmd += [os.path.join(csrc, "norm_act.hip"), os.path.join(TESTS, "gn_launch_driver.cpp")]
     elif p3:
         cmd += [os.path.join(csrc, "pack3d.hip"), os.path.join(TESTS, "p3_launch_driver.cpp")]
     elif patch:
         cmd += [os.path.join(csrc, "conv_patch.hip"), os.path.join(TESTS, "patch_launch_driver.cpp")]
+    elif wgrad:
+        cmd += [os.path.join(TESTS, "wgrad_launch_driver.cpp")]
     else:
         cmd += [os.path.join(TESTS, "conv_launch_driver.cpp")]
     cmd += ["-o", exe]
@@ -687,10 +693,141 @@ def patch_cases():
     return out
 
 
-def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False, patch=False):
+# ---- weight gradient (--wgrad): mte_conv2d_wgrad and its query.  (cin, cout, k, B, H, W) of tests/test_gpu_conv_variants.py: WGRAD_SHAPES, the launch-width test,
+# the stage test (with its element type); WGRAD9_SHAPES: (cin, cout, B, H, W, input as a slice of a buffer 64 channels wider)
+WGRAD_T_SHAPES = [(128, 128, 3, 2, 16, 64), (72, 96, 3, 2, 9, 40), (256, 64, 3, 1, 12, 32), (64, 128, 1, 3, 7, 24), (40, 256, 5, 1, 6, 168), (512, 512, 3, 1, 8, 20),
+                  (136, 264, 3, 2, 5, 80), (64, 64, 7, 1, 9, 48), (256, 256, 3, 2, 12, 32), (128, 256, 3, 2, 9, 40), (256, 128, 3, 1, 6, 168), (512, 256, 1, 2, 10, 24)]
+WGRAD_T_NINE = [(128, 128, 2, 16, 64, False), (256, 256, 2, 12, 32, False), (128, 256, 2, 8, 80, False), (512, 512, 1, 8, 48, False), (192, 128, 1, 6, 160, True),
+                (64, 384, 3, 10, 32, False), (256, 128, 1, 5, 64, True), (64, 128, 8, 24, 80, False), (2048, 128, 16, 3, 160, False), (128, 128, 1, 1, 32, False)]
+WGRAD_T_WIDTH = [(256, 256, 3, 2, 24, 64), (64, 64, 3, 1, 32, 64), (32, 32, 7, 1, 16, 64), (128, 128, 3, 1, 16, 96)]
+WGRAD_T_STAGE = [(128, 128, 3, BF16, 1, 24, 32), (64, 64, 5, BF16, 1, 48, 32), (256, 256, 1, BF16, 1, 48, 32), (32, 32, 3, BF16, 1, 48, 32), (64, 64, 3, F32, 1, 48, 32)]
+WGRAD_WGS, W9_WGS = 512, 128        # MTE_WGRAD_WGS, MTE_W9_WGS (csrc/wgrad_plan.hpp)
+DESC_BOUND = 0x7ff00000             # bytes a buffer descriptor addresses
+
+
+def wgrad_training_shapes():
+    """(B, H, W, Cin_p, N, KH, KW) of every mte_conv2d_wgrad call of the T8 training step, bench.py's size (profiles/r06_v7_conv_table.txt)"""
+    seen = []
+    with open(os.path.join(ROOT, "profiles", "r06_v7_conv_table.txt")) as f:
+        for line in f:
+            m = re.search(r"mte_conv2d_wgrad\s+B,H,W,Cin_p,N,KH,KW=\((.*)\)", line)
+            if m:
+                key = tuple(int(v) for v in m.group(1).split(","))
+                if key not in seen:
+                    seen.append(key)
+    return seen
+
+
+def wgrad_stage_cap(cin_p, n, kh, kw):
+    """the slabs kernels._conv_wgrad makes room for in front of mte_conv2d_wgrad"""
+    per = n * kh * kw * cin_p
+    wide = 256 if per <= (1 << 18) else (64 if per <= (1 << 19) else 32)
+    return max(1, min(wide, (96 << 20) // (4 * per)))
+
+
+def wgrad_case(entry, dtype, B, H, W, cin_p, N, kh, kw=None, ldx=None, ldy=None, cap=None, parts_out=1, shared=1, cus=256, knobs=None):
+    """cap: None = what kernels._conv_wgrad passes"""
+    kw = kh if kw is None else kw
+    return "%s %d %d %d %d %d %d %d %d %d %d %d %d %d %d %s" % (entry, dtype, B, H, W, cin_p, N, kh, kw, cin_p if ldx is None else ldx, N if ldy is None else ldy,
+                                                               wgrad_stage_cap(cin_p, N, kh, kw) if cap is None else cap, parts_out, shared, cus,
+                                                               ",".join("%d=%d" % kv for kv in knobs) if knobs else "-")
+
+
+def wgrad_cases():
+    out = []
+
+    def add(*a, **kw):
+        c = wgrad_case(*a, **kw)
+        if c not in out:
+            out.append(c)
+
+    # ---- the training step: bf16 and fp32, beside the data-gradient chain and alone (there with a second CU count), the stage of kernels._conv_wgrad and 0, 1, 2 slabs
+    for B, H, W, cin_p, N, kh, kw in wgrad_training_shapes():
+        add("nine_tap", BF16, B, H, W, cin_p, N, kh, kw)
+        for dtype in (BF16, F32):
+            for shared in (1, 0):
+                for cap in (None, 0, 1, 2):
+                    add("wgrad", dtype, B, H, W, cin_p, N, kh, kw, cap=cap, shared=shared)
+            add("wgrad", dtype, B, H, W, cin_p, N, kh, kw, shared=0, cus=64)
+    add("wgrad", 2, 8, 48, 160, 256, 256, 3)                              # an element type the library does not have
+    add("nine_tap", F32, 8, 48, 160, 256, 256, 3)
+
+    # ---- tests/test_gpu_conv_variants.py (K.use_wgrad_side_stream is on unless the test turns it off)
+    for cin, cout, k, B, H, W in WGRAD_T_SHAPES:
+        for kn in (None, [(8, 0)], [(8, 0), (4, 0)]):
+            add("wgrad", BF16, B, H, W, round8(cin), cout, k, knobs=kn)
+    for cin, cout, B, H, W, sliced in WGRAD_T_NINE:
+        for kn in ([(26, 1)], [(26, 0)], [(26, 2)], None):
+            add("wgrad", BF16, B, H, W, cin, cout, 3, ldx=cin + 64 if sliced else None, knobs=kn)
+        add("nine_tap", BF16, B, H, W, cin, cout, 3)
+    for cin, cout, k, B, H, W in WGRAD_T_WIDTH:
+        for shared in (1, 0):
+            add("wgrad", BF16, B, H, W, cin, cout, k, shared=shared)
+    for cin, cout, k, dtype, B, H, W in WGRAD_T_STAGE:
+        for shared in (1, 0):
+            for cap in (1, 2, 3):
+                add("wgrad", dtype, B, H, W, cin, cout, k, cap=cap, shared=shared)
+
+    # ---- both sides of every rule, one group at a time
+    for n in (32, 40, 64, 72, 128, 256, 264):                              # the tile ladders and the nine-tap kernel's whole tiles
+        for c in (32, 40, 64, 128, 136, 256):
+            for k in (3, 5):
+                add("wgrad", BF16, 8, 48, 160, c, n, k)
+            add("wgrad", F32, 8, 48, 160, c, n, 3)
+            add("nine_tap", BF16, 8, 48, 160, c, n, 3)
+            if n in (64, 128, 256) and c in (64, 128, 256):
+                for kn in ([(8, 0)], [(8, 2)], [(4, 0)], [(26, 0)], [(26, 2)]):
+                    add("wgrad", BF16, 8, 48, 160, c, n, 3, knobs=kn)
+                add("nine_tap", BF16, 8, 48, 160, c, n, 3, knobs=[(26, 0)])
+    for W in (24, 32, 40, 160, 168):                                       # row-aligned pixel blocks: W % 32 == 0 or W >= 160; the nine-tap forms: W % 32, W % 16 with H even
+        for H in (5, 6):
+            for dtype, c, n, k in ((BF16, 128, 128, 5), (F32, 128, 128, 5), (BF16, 32, 32, 3), (BF16, 32, 64, 3), (BF16, 128, 128, 3)):
+                add("wgrad", dtype, 2, H, W, c, n, k, cap=8)
+            for kn in (None, [(26, 2)]):
+                add("nine_tap", BF16, 2, H, W, 128, 128, 3, knobs=kn)
+            add("wgrad", BF16, 2, H, W, 128, 128, 3, cap=8, knobs=[(26, 2)])
+    for H in (11, 12, 23, 24, 25, 36, 49, 50, 100):                        # nine-tap, one K-step per row: at least 12 K-steps per split, rounded up to the four ring slots
+        for cus in (256, 64):
+            for cap in (2, 8):
+                add("wgrad", BF16, 1, H, 32, 128, 128, 3, cap=cap, shared=0, cus=cus)
+    for H in (15, 16, 17, 31, 32, 33, 48, 49):                             # one pixel block per row: at least 16 per split
+        for dtype, c, n, k in ((BF16, 64, 64, 5), (F32, 64, 64, 5), (BF16, 32, 32, 3)):
+            add("wgrad", dtype, 1, H, 32, c, n, k, cap=8)
+    for k, kw in ((1, 1), (7, 7), (2, 2), (4, 4), (3, 5), (5, 3), (1, 3)):  # even and mixed kernel sizes are not refused
+        for dtype in (BF16, F32):
+            add("wgrad", dtype, 2, 24, 64, 128, 128, k, kw)
+        add("nine_tap", BF16, 2, 24, 64, 128, 128, k, kw)
+    for c, n in ((12, 32), (32, 12), (128, 132), (68, 128)):               # channel counts that are no multiple of 8
+        add("wgrad", BF16, 2, 24, 64, c, n, 3)
+    # a stride that puts each descriptor bound just inside and just outside: the nine-tap kernel's x, the generic kernels' x, dy (both element types)
+    for B, H, W, c, n in ((8, 48, 160, 256, 256), (8, 96, 320, 128, 128)):
+        M = B * H * W
+        for dtype, es in ((BF16, 2), (F32, 4)):
+            edges = [((DESC_BOUND - 1) // es - c) // (M + 3)] + ([(DESC_BOUND - 1) // 2 // (M + 2 * W + 16)] if dtype == BF16 else [])
+            for edge in edges:
+                for ldx in (edge // 8 * 8, edge // 8 * 8 + 8):
+                    add("wgrad", dtype, B, H, W, c, n, 3, ldx=ldx)
+            edge = ((DESC_BOUND - 1) // es - n) // (M - 1)
+            for ldy in (edge // 8 * 8, edge // 8 * 8 + 8):
+                add("wgrad", dtype, B, H, W, c, n, 3, ldy=ldy)
+    for dtype, c, n, k in ((BF16, 256, 256, 3), (BF16, 512, 128, 5), (BF16, 32, 32, 3), (F32, 128, 128, 3)):      # no parts_out: no nine-tap kernel
+        for shared in (1, 0):
+            add("wgrad", dtype, 8, 48, 160, c, n, k, parts_out=0, shared=shared)
+    # the width knobs, and the whole-rounds search with several CU counts
+    for c, n, k in ((256, 256, 3), (512, 128, 5), (128, 128, 1), (4096, 256, 3)):
+        for shared in (1, 0):
+            for kn in ([(9, 256)], [(9, 1024)], [(27, 0)], [(27, 64)], [(27, 256)], [(26, 0), (9, 256)], [(26, 0), (8, 0)]):
+                add("wgrad", BF16, 8, 48, 160, c, n, k, shared=shared, knobs=kn)
+        for cus in (64, 128, 304):
+            add("wgrad", BF16, 8, 48, 160, c, n, k, shared=0, cus=cus)
+            add("wgrad", BF16, 8, 48, 160, c, n, k, shared=0, cus=cus, knobs=[(26, 0)])
+    return out
+
+
+def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False, patch=False, wgrad=False):
     with tempfile.TemporaryDirectory() as tmp:
-        cs = gn_cases() if gn else p3_cases() if p3 else patch_cases() if patch else cases()
-        return run(build(tmp, dev, csrc, extra, gn, p3, patch), cs if dev else [c for c in cs if c.endswith(" -")])
+        cs = gn_cases() if gn else p3_cases() if p3 else patch_cases() if patch else wgrad_cases() if wgrad else cases()
+        return run(build(tmp, dev, csrc, extra, gn, p3, patch, wgrad), cs if dev else [c for c in cs if c.endswith(" -")])
 
 
 def load_table(path=TABLE):
@@ -708,10 +845,11 @@ if __name__ == "__main__":
     ap.add_argument("--gn", action="store_true", help="GroupNorm (norm_act.hip, tests/gn_launch_table.json)")
     ap.add_argument("--p3", action="store_true", help="conv3d pack / unpack (pack3d.hip, tests/p3_launch_table.json)")
     ap.add_argument("--patch", action="store_true", help="LDS-patch convolution (conv_patch.hip, tests/patch_launch_table.json)")
+    ap.add_argument("--wgrad", action="store_true", help="weight gradient (mte_conv2d_wgrad: conv_igemm.hip, conv_wgrad9.hip, tests/wgrad_launch_table.json)")
     a = ap.parse_args()
-    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3, patch=a.patch)
+    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3, patch=a.patch, wgrad=a.wgrad)
     for ln in lines:
         json.loads(ln)
-    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else PATCH_TABLE if a.patch else TABLE) if a.write else a.out, "w") as f:
+    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else PATCH_TABLE if a.patch else WGRAD_TABLE if a.wgrad else TABLE) if a.write else a.out, "w") as f:
         f.write("[\n" + ",\n".join(lines) + "\n]\n")
     print("%d cases" % len(lines))

@@ -1,7 +1,8 @@
 // Launch recorder for the host code that chooses kernels (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip /
-// norm_act.hip / pack3d.hip / conv_patch.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync and hipGetLastError are redefined, so no
+// conv_wgrad9.hip / norm_act.hip / pack3d.hip / conv_patch.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync, hipGetLastError,
+// hipGetDevice and hipDeviceGetAttribute (answered with the CU count the driver sets) are redefined, so no
 // call reaches the HIP runtime: every launch is appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the
-// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args, P3LArgs, PatchArgs or PatchWgradArgs argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
+// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args, P3LArgs, PatchArgs, PatchWgradArgs, WgradArgs or Wgrad9Args argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
 // kernels of mte_memset_async in common.hpp) is a line of its own: which buffer and how many bytes.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -55,6 +56,18 @@ template <typename A, typename = void> struct is_patch_args : std::false_type {}
 template <typename A> struct is_patch_args<A, std::void_t<decltype(A::r1_inv), decltype(A::x2), decltype(A::gn_rec)>> : std::true_type {};
 template <typename A, typename = void> struct is_patch_wgrad_args : std::false_type {};      // PatchWgradArgs
 template <typename A> struct is_patch_wgrad_args<A, std::void_t<decltype(A::lddy), decltype(A::groups), decltype(A::part_stride)>> : std::true_type {};
+template <typename A, typename = void> struct is_wgrad_args : std::false_type {};          // WgradArgs: the LDS-DMA and register-staged weight gradients
+template <typename A> struct is_wgrad_args<A, std::void_t<decltype(A::blocks_per_split), decltype(A::tiles_n), decltype(A::part_stride)>> : std::true_type {};
+template <typename A, typename = void> struct is_wgrad9_args : std::false_type {};         // Wgrad9Args: the nine-tap weight gradient
+template <typename A> struct is_wgrad9_args<A, std::void_t<decltype(A::units_per_split), decltype(A::base), decltype(A::part_stride)>> : std::true_type {};
+// compute units the device query answers (the weight-gradient driver sets it per case): no case depends on whether the machine has a GPU
+inline int& cus() { static int n = 256; return n; }
+inline hipError_t get_device(int* dev) { *dev = 0; return hipSuccess; }
+inline hipError_t device_attribute(int* v, hipDeviceAttribute_t what, int) {       // the CU count and nothing else
+    if (what != hipDeviceAttributeMultiprocessorCount) return hipErrorInvalidValue;
+    *v = cus();
+    return hipSuccess;
+}
 
 // (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other fields 0, a pointer null)
 template <typename A> void arg_fields(const A& a) {
@@ -80,6 +93,12 @@ template <typename A> void arg_fields(const A& a) {
         if (!with.empty()) log() += ",\"with\":\"" + with.substr(1) + "\"";
     } else if constexpr (is_patch_wgrad_args<A>::value) {
         field("groups", a.groups, 0); field("part_stride", a.part_stride, 0);
+    } else if constexpr (is_wgrad_args<A>::value) {
+        field("tiles_n", a.tiles_n, 0); field("tiles_c", a.tiles_c, 0); field("splits", a.splits, 1); field("blocks_per_split", a.blocks_per_split, 0);
+        field("part_stride", a.part_stride, 0);
+    } else if constexpr (is_wgrad9_args<A>::value) {
+        field("tiles_c", a.tiles_c, 0); field("base", a.base, 0); field("units", a.units, 0); field("units_per_split", a.units_per_split, 0);
+        field("part_stride", a.part_stride, 0);
     }
 }
 
@@ -114,3 +133,5 @@ inline hipError_t set_attribute(const void* k, hipFuncAttribute, int v) { grante
 #define hipFuncSetAttribute(...) mte_rec::set_attribute(__VA_ARGS__)
 #define hipMemsetAsync(p, value, bytes, stream) mte_rec::clear(p, bytes)
 #define hipGetLastError() hipSuccess
+#define hipGetDevice(dev) mte_rec::get_device(dev)
+#define hipDeviceGetAttribute(...) mte_rec::device_attribute(__VA_ARGS__)

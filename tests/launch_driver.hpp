@@ -1,4 +1,4 @@
-// What the drivers of the launch recorder share (conv_launch_driver.cpp, gn_launch_driver.cpp, p3_launch_driver.cpp, patch_launch_driver.cpp): the stand-ins for the rest of the library, the knob list of a
+// What the drivers of the launch recorder share (conv_launch_driver.cpp, gn_launch_driver.cpp, p3_launch_driver.cpp, patch_launch_driver.cpp, wgrad_launch_driver.cpp): the stand-ins for the rest of the library, the knob list of a
 // case, and the loop that runs every case in a child process of its own.
 #pragma once
 #include <stdio.h>
@@ -28,8 +28,6 @@ void __hipRegisterFunction(void**, const void*, char*, const char*, unsigned, vo
 void __hipRegisterVar(void**, void*, char*, char*, int, size_t, int, int) {}
 void __hipUnregisterFatBinary(void**) {}
 }
-int g_wgrad9 = 1, g_wgrad9_wgs = 0;
-int wgrad9_launch(const void*, long, const void*, long, float*, int, int*, int, int, int, int, int, hipStream_t) { return -3; }
 
 #ifdef MTE_REC_COVERAGE
 extern "C" void __gcov_dump(void);

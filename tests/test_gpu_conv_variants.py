@@ -123,8 +123,7 @@ def test_dma_wgrad_matches_register_staged_wgrad(shape, devlib):
         K.lib.mte_debug_set(4, 0)
         r = _run(*shape, patch=False)
     finally:
-        K.lib.mte_debug_set(4, 1)
-        K.lib.mte_debug_set(8, 1)
+        K.lib.mte_debug_set(33, 0)                     # every weight-gradient knob back to its default (WgradKnobs{}, csrc/wgrad_plan.hpp)
     assert rel_err(a["dw"], r["dw"]) < 2e-4
     assert rel_err(big["dw"], r["dw"]) < 2e-4
     assert torch.equal(a["y"], r["y"])                 # (the forward kernel is the same in all three runs and bit-reproducible)
@@ -427,7 +426,7 @@ def test_nine_tap_wgrad_matches_the_per_tap_kernel_and_fp64(shape, devlib):
         (y * gf.double()).sum().backward()
         assert rel_err(a.cpu(), wd.grad) < 2e-5, rel_err(a.cpu(), wd.grad)
     finally:
-        devlib.mte_debug_set(26, 1)
+        devlib.mte_debug_set(33, 0)                    # every weight-gradient knob back to its default (WgradKnobs{}, csrc/wgrad_plan.hpp)
         K.use_patch_kernels(True)
 
 
@@ -514,6 +513,54 @@ def test_weight_gradient_launch_width_follows_the_schedule_and_not_the_result(ci
     scale = float(ref.abs().max())
     for shared in (True, False):
         assert float((out[shared].double() - ref).abs().max()) < 2e-5 * scale
+
+
+# The smallest shapes that still reach more than one pixel split, and the form plan_wgrad (csrc/wgrad_plan.hpp) gives each -- tests/wgrad_launch_table.json has
+# these lines, recorded on the CPU.  `most`: the pixel splits the shape gets where the stage has room (slab-writing families), 0 = the register-staged family.
+WGRAD_STAGE_SHAPES = [  # cin, cout, k, dtype, B, H, W, most
+    (128, 128, 3, "bf16", 1, 24, 32, 2),       # nine-tap (conv_wgrad9_kernel<1>), 24 K-steps: two splits of 12 where the cap allows
+    (64, 64, 5, "bf16", 1, 48, 32, 3),         # LDS-DMA 64 x 128 tile (conv_wgrad_dma_kernel<2, 2, 1, 2, true>), 48 pixel blocks: up to three splits of 16
+    (256, 256, 1, "bf16", 1, 48, 32, 3),       # LDS-DMA 16-wave 256 x 256 tile (conv_wgrad_dma_kernel<4, 4, 2, 2, true>): up to three splits
+    (32, 32, 3, "bf16", 1, 48, 32, 0),         # register-staged (conv_wgrad_kernel<bf16, 1, 4, 1, 1, true>): clears slab 0 itself and adds three splits into it
+    (64, 64, 3, "fp32", 1, 48, 32, 0),         # register-staged (conv_wgrad_kernel<float, 2, 2, 1, 2, true>): the same
+]
+
+
+@pytest.mark.parametrize("stage_parts", [1, 2, 3])
+@pytest.mark.parametrize("shape", WGRAD_STAGE_SHAPES)
+def test_weight_gradient_writes_no_slab_beyond_its_stage(shape, stage_parts):
+    """mte_conv2d_wgrad through the C interface with a stage of `stage_parts` slabs: it reports 1 .. stage_parts slabs, leaves everything behind them alone (a
+    NaN-filled slab more than it was given, and the unused ones), the slabs it reports add up to the fp64 weight gradient of the same rounded operands, and the
+    slab-writing families (plain stores) reproduce themselves bit for bit.  The register-staged family ignores the cap: one slab, cleared by the launch itself."""
+    import ctypes
+    from mindtheedge_amd import kernels as K
+    cin, cout, k, dtype, B, H, W, most = shape
+    tdt = torch.bfloat16 if dtype == "bf16" else torch.float32
+    g = torch.Generator().manual_seed(cin + 7 * cout + k + stage_parts)
+    xf = (torch.rand(B, cin, H, W, generator=g) * 2 - 1).bfloat16().float()
+    gf = (torch.rand(B, cout, H, W, generator=g) * 2 - 1).bfloat16().float()
+    x, dy = K.as_act(xf.cuda(), tdt), K.as_act(gf.cuda(), tdt)
+    (xp, ldx), (dyp, lddy) = K._pl(x), K._pl(dy)
+    st = torch.cuda.current_stream().cuda_stream
+
+    def run():
+        stage = torch.full((stage_parts + 1, cout, k * k, cin), float("nan"), dtype=torch.float32, device="cuda")
+        parts = ctypes.c_int(-1)
+        # (the binding raises MteError, naming the code, on any return but MTE_OK)
+        assert K.lib.mte_conv2d_wgrad(xp, ldx, dyp, lddy, stage.data_ptr(), stage_parts, ctypes.byref(parts), B, H, W, cin, cout, k, k, K._dt(x), st) is None
+        torch.cuda.synchronize()
+        return stage.cpu(), parts.value
+
+    stage, parts = run()
+    assert 1 <= parts <= stage_parts
+    assert parts == (min(stage_parts, most) if most else 1)
+    assert bool(torch.isnan(stage[parts:]).all())
+    dw = stage[:parts].double().sum(0).reshape(cout, k, k, cin).permute(0, 3, 1, 2)             # [N][tap][Cin_p] -> OIHW
+    ref = torch.nn.grad.conv2d_weight(xf.double(), (cout, cin, k, k), gf.double(), padding=k // 2)
+    assert float((dw - ref).abs().max()) < 2e-5 * float(ref.abs().max())
+    if most:
+        again, parts2 = run()
+        assert parts2 == parts and torch.equal(again[:parts], stage[:parts])
 
 
 @pytest.mark.parametrize("C,cout,k,B,H2,W2", [(32, 32, 7, 2, 24, 64), (32, 32, 7, 1, 13, 40), (64, 64, 5, 2, 16, 48), (8, 32, 3, 1, 9, 33), (64, 40, 5, 1, 8, 24)])
