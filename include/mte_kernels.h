@@ -116,7 +116,10 @@ int mte_colsum(const void* y, long ld, long M, int N, float* out, int dtype, mte
 
 /* ---- LDS-patch convolution for the high-resolution, few-channel layers (bf16, C_out <= 64, W % 32 == 0, k in {1,3,5,7}):
  * same math as mte_conv2d_igemm / mte_conv2d_wgrad, different tiling (the 8x32-pixel tile's input patch is staged once
- * per 32-channel slice and reused by all k*k taps).  *_supported and *_pack_elems are queries (they return a value). */
+ * per 32-channel slice and reused by all k*k taps).  *_supported and *_pack_elems are queries (they return a value).
+ * mte_conv2d_patch_fwd: y = bf16(conv(x) + bias), fp32 sums rounded to nearest even once; accumulate = 1: y = bf16(float(bf16(conv(x) + bias)) + y), the two
+ * roundings of mte_conv2d_igemm -- the two families are bit-identical wherever the fp32 sum does not depend on its order.  Pixel strides ldx >= Cin_p and
+ * ldy >= N: channel slices of wider buffers are read and written in place, nothing outside the N output channels of a pixel is touched. */
 int mte_conv2d_patch_supported(int W, int Cin_p, int N, int KH, int KW, int dtype);
 int mte_conv2d_patch_wgrad_supported(int W, int Cin_p, int N, int KH, int KW, int dtype);   /* + 3x3 layers with 65..128 output channels (weight gradient only) */
 long mte_conv2d_patch_pack_elems(int Cin_p, int N, int KH, int KW);

@@ -35,11 +35,13 @@ template <> struct Elem<bf16_t> {
     static constexpr int PER16 = 8;                      // elements per 16-byte chunk
     __device__ static __forceinline__ float ld(const bf16_t* p) { return bf2f(*p); }
     __device__ static __forceinline__ void st(bf16_t* p, float v) { *p = f2bf(v); }
+    __device__ static __forceinline__ float rnd(float v) { return bf2f(f2bf(v)); }     // v as it reads back after st
 };
 template <> struct Elem<float> {
     static constexpr int PER16 = 4;
     __device__ static __forceinline__ float ld(const float* p) { return *p; }
     __device__ static __forceinline__ void st(float* p, float v) { *p = v; }
+    __device__ static __forceinline__ float rnd(float v) { return v; }
 };
 
 // 16-byte chunk <-> 8 floats (bf16) / 4 floats (f32).  Always fills/consumes v[0..PER16).

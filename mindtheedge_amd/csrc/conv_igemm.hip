@@ -648,7 +648,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_igemm_kernel(ConvArgs
                     const long pm = a.rows ? (long)a.rows[m] : m;
                     if (a.splits > 1) a.ws[((long)split * a.M + m) * a.N + n] = acc[i][j][e];
                     else if (a.out_f32) ((float*)a.y)[pm * a.ldy + n] = a.accum ? v + ((float*)a.y)[pm * a.ldy + n] : v;
-                    else Elem<T>::st((T*)a.y + pm * a.ldy + n, a.accum ? v + Elem<T>::ld((const T*)a.y + pm * a.ldy + n) : v);
+                    // (accum: conv + bias rounded to T first, as the LDS-staged epilogue above stages it -- ConvArgs.accum, two roundings in every form)
+                    else Elem<T>::st((T*)a.y + pm * a.ldy + n, a.accum ? Elem<T>::rnd(v) + Elem<T>::ld((const T*)a.y + pm * a.ldy + n) : v);
                 }
             }
         }
@@ -656,7 +657,8 @@ __global__ __launch_bounds__(WM * WN * 64, MINW) void conv_igemm_kernel(ConvArgs
 }
 
 
-// y = T(sum_s ws[s] + bias) after a split-K launch: the slabs are added in split order (fixed), rounded once
+// y = T(sum_s ws[s] + bias) after a split-K launch: the slabs are added in split order (fixed), rounded once; accum: y = T(float(T(sum + bias)) + y), the
+// two roundings of every unsplit form (ConvArgs.accum)
 template <typename T>
 __global__ void splitk_finish_kernel(const float* __restrict__ ws, int splits, const float* __restrict__ bias, T* y, long ldy, long M, int N, int accum) {
     const long n4 = M * N / 4;
@@ -665,7 +667,10 @@ __global__ void splitk_finish_kernel(const float* __restrict__ ws, int splits, c
         f32x4_t v = ((const f32x4_t*)ws)[i];
         for (int s = 1; s < splits; ++s) v += ((const f32x4_t*)ws)[(long)s * n4 + i];
 #pragma unroll
-        for (int k = 0; k < 4; ++k) Elem<T>::st(y + m * ldy + n + k, v[k] + (bias ? bias[n + k] : 0.f) + (accum ? Elem<T>::ld(y + m * ldy + n + k) : 0.f));
+        for (int k = 0; k < 4; ++k) {
+            const float r = v[k] + (bias ? bias[n + k] : 0.f);
+            Elem<T>::st(y + m * ldy + n + k, accum ? Elem<T>::rnd(r) + Elem<T>::ld(y + m * ldy + n + k) : r);
+        }
     }
 }
 

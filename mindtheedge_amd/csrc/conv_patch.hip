@@ -52,7 +52,8 @@ struct PatchArgs {
     const float* bias;
     bf16_t* y; long ldy;
     int B, H, W, Cin_p, N;
-    int accum;                                     // 1: y += conv (fp32 sum, rounded once)
+    int accum;                                     // 1: y += conv -- conv + bias is staged in LDS as bf16, the old value added in fp32, the sum rounded again: the two
+                                                   // roundings of every implicit-GEMM tile form (ConvArgs.accum, conv_args.hpp), bit-identical with them
     // rank-1 term (3x3 second form only, mte_conv2d_patch_fwd_rank1): y += conv_1(nearest_up2(r1_inv)) with one more input channel's weights
     const float* r1_inv;                           // [B][H/2][W/2] fp32, or nullptr
     const float* r1_w; long r1_ws;                 // element (n, tap) at r1_w[n * r1_ws + tap]
