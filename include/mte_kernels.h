@@ -301,6 +301,20 @@ int mte_edge_loss_multi_fwd(const void* scales, int nscales, int B, int from_inv
 int mte_edge_loss_multi_bwd(const void* scales, int nscales, int B, int from_inv, int is_grad, int is_sigmoid, float thresh,
                             const float* coef, const float* gout, const float* gt_depth, const float* silog_aux, const float* silog_gout,
                             mte_stream_t stream);
+/* The same for TWO predictions against one set of labels (models/SemiSupEdgeCompletionModel.py:128-165: branch 0 = the RGB prediction,
+ * branch 1 = the RGB+LiDAR prediction) in ONE forward and ONE backward launch that read the labels once.  Only the training configuration
+ * is built: inverse depth in, Sobel + normals + sigmoid, every scale with W % 4 == 0, 16-byte-aligned bases and normals, no mask, no
+ * edge-map output.  Anything else answers MTE_ERR_UNSUPPORTED and launches nothing: the caller makes two mte_edge_loss_multi_* calls.
+ *   work   : mte_edge_loss_pair_work_elems() doubles (content on entry ignored; zero on entry under MTE_OPT_LOSS_PREZEROED)
+ *   losses [2][nscales], coef [2][nscales][2B+1], silog_loss [2], silog_aux [2][2]; gt_depth nullable
+ *   backward: dpred[br]_s <- gout[br][s] * d loss / d pred[br]_s (+ silog_gout[br] * d silog / d pred[br]_0); gout / silog_gout: device, nullable = 1 */
+typedef struct { const float* pred[2]; float* dpred[2]; const float* edge; const float* normal; int H; int W; } mte_edge_pair_scale;
+long mte_edge_loss_pair_work_elems(const void* scales, int nscales, int B);
+int mte_edge_loss_pair_fwd(const void* scales, int nscales, int B, float thresh, float weight, float pos_to_neg,
+                           const float* gt_depth, double* work, float* losses, float* coef,
+                           float* silog_loss, float* silog_aux, mte_stream_t stream);
+int mte_edge_loss_pair_bwd(const void* scales, int nscales, int B, float thresh, const float* coef, const float* gout,
+                           const float* gt_depth, const float* silog_aux, const float* silog_gout, mte_stream_t stream);
 /* single-scale entry points (GradLoss / GradLayer called on their own): the same kernels with one scale */
 long mte_edge_loss_sums_elems(int B, int H, int W);   /* doubles `sums` must hold: B*6 + 4 results, the arrival ticket, the per-workgroup partial sums */
 int mte_edge_loss_fwd(const float* pred, const float* edge, const float* normal, const float* mask, double* sums, float* gmap,

@@ -6,6 +6,7 @@ import ctypes
 
 import torch
 
+from . import _lib as _L
 from . import kernels as _K          # (imported at the END of kernels.py: its helpers are looked up at call time)
 from ._lib import MteError          # noqa: F401  (the library handle is kernels.lib at call time: bench.py swaps it for a timing proxy)
 
@@ -166,6 +167,101 @@ class DepthLossesFn(torch.autograd.Function):
         _K.lib.mte_edge_loss_multi_bwd(ctypes.addressof(arr), S, B, from_inv, 1, 1, thresh, coef.data_ptr(), gl.data_ptr(), _K._ptr(gt),
                                     _K._ptr(aux), gl.data_ptr() + 4 * S if gt is not None else 0, _K._stream())
         return (None,) * 8 + tuple(dpreds)
+
+
+class _EdgePairScale(ctypes.Structure):   # mte_edge_pair_scale of include/mte_kernels.h
+    _fields_ = [("pred", ctypes.c_void_p * 2), ("dpred", ctypes.c_void_p * 2), ("edge", ctypes.c_void_p), ("normal", ctypes.c_void_p),
+                ("H", ctypes.c_int), ("W", ctypes.c_int)]
+
+
+def _pair_raw(name, *args):
+    """A pair entry point called raw, to see MTE_ERR_UNSUPPORTED (-3, include/mte_kernels.h) instead of an exception: -> True when it ran"""
+    rc = getattr(_L.lib.load(), name)(*args)
+    if rc not in (0, -3):
+        raise MteError("%s failed: %s" % (name, _L._ERRORS.get(rc, rc)))
+    return rc == 0
+
+
+class DepthLossesPairFn(torch.autograd.Function):
+    """Every loss term of SemiSupEdgeCompletionModel.forward (models/SemiSupEdgeCompletionModel.py:128-165) in ONE forward and ONE backward
+    launch: the depth-edge loss of all scales and, when `gt_depth` is given, the sparse silog loss of scale 0, for the RGB predictions
+    (branch 0) and the RGB+LiDAR predictions (branch 1) against the same labels, which are read once (csrc/edge_loss_pair.hip).
+    apply(weight, pos_to_neg, thresh, gt_depth, edges, normals, *preds_rgb, *preds_rgbd) -> fp32 [2, S (+1)]: per branch weight * balanced BCE
+    per scale, then that branch's silog loss when gt_depth is given.  Where the library answers MTE_ERR_UNSUPPORTED (a scale outside the
+    training configuration: no normals, W % 4 != 0, an unaligned base) the same numbers come from two DepthLossesFn applications."""
+
+    @staticmethod
+    def _scales(preds, edges, normals, dpreds):
+        S = len(edges)
+        arr = (_EdgePairScale * S)()
+        for s, o in enumerate(arr):
+            for br in range(2):
+                o.pred[br] = preds[br * S + s].data_ptr()
+                o.dpred[br] = None if dpreds is None else dpreds[br * S + s].data_ptr()
+            o.edge, o.normal = edges[s].data_ptr(), _K._ptr(normals[s])
+            o.H, o.W = edges[s].shape[-2], edges[s].shape[-1]
+        return arr
+
+    @staticmethod
+    def forward(ctx, weight, pos_to_neg, thresh, gt_depth, edges, normals, *preds):
+        S = len(edges)
+        if len(preds) != 2 * S or not 1 <= S <= 4:
+            raise MteError("%d label scales (1 to 4) need %d predictions, got %d" % (S, 2 * S, len(preds)))
+        B = preds[0].shape[0]
+        dev = preds[0].device
+        preds = [p.contiguous().float() for p in preds]
+        edges = [e.contiguous().float() for e in edges]
+        normals = [None if n is None else n.contiguous().float() for n in normals]
+        gt = None if gt_depth is None else gt_depth.contiguous().float()
+        for i, p in enumerate(preds):
+            e, n = edges[i % S], normals[i % S]
+            if tuple(p.shape) != tuple(e.shape) or (n is not None and tuple(n.shape) != tuple(e.shape)):
+                raise MteError("prediction / label shapes differ: %s vs %s" % (tuple(p.shape), tuple(e.shape)))
+        arr = DepthLossesPairFn._scales(preds, edges, normals, None)
+        n_out = S + (1 if gt is not None else 0)
+        work = _K._zeros((_K.lib.mte_edge_loss_pair_work_elems(ctypes.addressof(arr), S, B),), torch.float64, dev)
+        losses = torch.empty((2, S), dtype=torch.float32, device=dev)
+        coef = torch.empty((2 * S * (2 * B + 1),), dtype=torch.float32, device=dev)
+        sil = torch.empty((2,), dtype=torch.float32, device=dev) if gt is not None else None
+        aux = torch.empty((4,), dtype=torch.float32, device=dev) if gt is not None else None
+        ctx.pair = _pair_raw("mte_edge_loss_pair_fwd", ctypes.addressof(arr), S, B, float(thresh), float(weight), float(pos_to_neg), _K._ptr(gt),
+                             work.data_ptr(), losses.data_ptr(), coef.data_ptr(), _K._ptr(sil), _K._ptr(aux), _K._stream())
+        ctx.cfg = (S, B, float(thresh), [n is not None for n in normals])
+        if ctx.pair:
+            ctx.save_for_backward(coef, gt, aux, *preds, *edges, *[n for n in normals if n is not None])
+            return losses if gt is None else torch.cat([losses, sil[:, None]], dim=1)
+        # outside the training configuration: two single launches on the existing kernels, the same outputs
+        ctx.single = []
+        out = torch.empty((2, n_out), dtype=torch.float32, device=dev)
+        for br in range(2):
+            with torch.enable_grad():
+                leaves = [p.detach().requires_grad_(True) for p in preds[br * S:(br + 1) * S]]
+                one = DepthLossesFn.apply(weight, pos_to_neg, thresh, True, None, gt, edges, normals, *leaves)
+            ctx.single.append((leaves, one))
+            out[br] = one.detach()
+        return out
+
+    @staticmethod
+    def backward(ctx, glosses):
+        S, B, thresh, has_n = ctx.cfg
+        gl = glosses.contiguous().float()
+        if not ctx.pair:
+            grads = []
+            for br, (leaves, one) in enumerate(ctx.single):
+                grads += list(torch.autograd.grad(one, leaves, gl[br]))
+            return (None,) * 6 + tuple(grads)
+        coef, gt, aux = ctx.saved_tensors[:3]
+        rest = ctx.saved_tensors[3:]
+        preds, edges, nrm = rest[:2 * S], rest[2 * S:3 * S], list(rest[3 * S:])
+        normals = [nrm.pop(0) if h else None for h in has_n]
+        dpreds = [torch.empty_like(p) for p in preds]
+        arr = DepthLossesPairFn._scales(preds, edges, normals, dpreds)
+        gedge = gl[:, :S].contiguous()
+        gsil = gl[:, S].contiguous() if gt is not None else None
+        if not _pair_raw("mte_edge_loss_pair_bwd", ctypes.addressof(arr), S, B, thresh, coef.data_ptr(), gedge.data_ptr(), _K._ptr(gt),
+                         _K._ptr(aux), _K._ptr(gsil), _K._stream()):
+            raise MteError("mte_edge_loss_pair_bwd refused what mte_edge_loss_pair_fwd took")
+        return (None,) * 6 + tuple(dpreds)
 
 
 class SilogFn(torch.autograd.Function):

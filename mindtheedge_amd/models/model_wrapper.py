@@ -39,8 +39,10 @@ def setup_depth_edge_loss(config):
 def setup_model(config, prepared, **kwargs):
     model = load_class(config.model.name, paths=['models'])(**{**config.model.loss, **kwargs})
     if 'depth_net' in model.network_requirements:
-        # the depth-edge estimator runs the RGB+LiDAR pass: its network owns the sparse branch (with_san is not a reference key)
-        extra = {'with_san': True} if config.model.name.startswith('EdgeEstimation') and 'with_san' not in config.model.depth_net else {}
+        # the depth-edge estimator and the completion models run the RGB+LiDAR pass: their network owns the sparse branch (with_san is not a
+        # reference key; an explicit model.depth_net.with_san wins)
+        wants_san = config.model.name.startswith('EdgeEstimation') or config.model.name.endswith('CompletionModel')
+        extra = {'with_san': True} if wants_san and 'with_san' not in config.model.depth_net else {}
         model.add_depth_net(setup_depth_net(config.model.depth_net, prepared, **extra))
     if 'pose_net' in model.network_requirements:
         raise NotImplementedError("pose networks are outside this build's scope")
@@ -160,6 +162,10 @@ class ModelWrapper(nn.Module):
             from ..utils.edge import compute_edge_metrics_from_depth
             gt_edge = batch['edge'][0, 0].float() * 255
             metrics['edges'] = compute_edge_metrics_from_depth(depth[0, 0], gt_edge)
+            if 'input_depth' in batch and getattr(self.model.depth_net, 'with_san', False):
+                # reference :357-368: the same metrics of the RGB+LiDAR prediction (the completion models validate both)
+                inv_input = self.depth(batch['rgb'], batch['input_depth'], rgb_edge=batch.get('rgb_edge'))['inv_depths'][0][0][:, 0:1, :, :]
+                metrics['edges_input'] = compute_edge_metrics_from_depth(inv2depth(inv_input)[0, 0], gt_edge)
         return {'metrics': metrics, 'inv_depth': inv_depth_pp}
 
     def validation_step(self, batch, *args):
@@ -185,19 +191,20 @@ class ModelWrapper(nn.Module):
         K.check_device_errors()                              # the validation forwards of the epoch have finished (host read above)
         out = {'{}-{}{}'.format(self.metrics_name, key, mode): float(mean[i, j])
                for i, mode in enumerate(self.metrics_modes) for j, key in enumerate(self.metrics_keys)}
-        edge_rows = [o['edges'] for o in output_data_batch if 'edges' in o]
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        if edge_rows or multi:                               # (precision, recall, F1) x the three Canny settings, reference :431-438
-            etotal = torch.stack(edge_rows).double().sum(0) if edge_rows else torch.zeros(9, dtype=torch.float64, device=dev)
-            ecount = torch.tensor(float(len(edge_rows)), device=etotal.device, dtype=etotal.dtype)
-            if multi:                                        # unconditional: a rank without edge rows must not leave the others waiting
-                dist.all_reduce(etotal)
-                dist.all_reduce(ecount)
-        if (edge_rows or multi) and float(ecount) > 0:
-            emean = (etotal / ecount).cpu()
-            for k in range(emean.numel() // 3):
-                for j, key in enumerate(('precision', 'recall', 'f1')):
-                    out['edges-{}_{}'.format(key, k)] = float(emean[3 * k + j])
+        for name in ('edges', 'edges_input'):                # 'edges_input': the RGB+LiDAR prediction's (evaluate_depth, reference :365-368)
+            edge_rows = [o[name] for o in output_data_batch if name in o]
+            if edge_rows or multi:                           # (precision, recall, F1) x the three Canny settings, reference :431-438
+                etotal = torch.stack(edge_rows).double().sum(0) if edge_rows else torch.zeros(9, dtype=torch.float64, device=dev)
+                ecount = torch.tensor(float(len(edge_rows)), device=etotal.device, dtype=etotal.dtype)
+                if multi:                                    # unconditional: a rank without edge rows must not leave the others waiting
+                    dist.all_reduce(etotal)
+                    dist.all_reduce(ecount)
+            if (edge_rows or multi) and float(ecount) > 0:
+                emean = (etotal / ecount).cpu()
+                for k in range(emean.numel() // 3):
+                    for j, key in enumerate(('precision', 'recall', 'f1')):
+                        out['{}-{}_{}'.format(name, key, k)] = float(emean[3 * k + j])
         return out
 
     def depth(self, *args, **kwargs):
