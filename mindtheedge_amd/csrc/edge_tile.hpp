@@ -1,5 +1,5 @@
-// Tile geometry and per-pixel helpers shared by the edge-loss kernels (edge_loss.hip: the four-scale training launch; edge_loss_kinds.hip: the
-// other loss kinds, one scale per launch).  A workgroup of 256 threads is one 64 x 32-pixel tile of one sample; a thread owns 4 consecutive
+// Tile geometry and per-pixel helpers shared by the edge-loss kernels (edge_loss.hip: the generic four-scale kernels; edge_fast.hpp: the training
+// configuration's, for one or two predictions per label set; edge_loss_kinds.hip: the other loss kinds, one scale per launch).  A workgroup of 256 threads is one 64 x 32-pixel tile of one sample; a thread owns 4 consecutive
 // pixels of rows r0 and r0 + 16, so every global access is a 16-byte load / store; the prediction tile + halo is staged in LDS as DEPTH.
 #pragma once
 #include "common.hpp"

@@ -2,8 +2,8 @@
 // workgroup that draws the last ticket adds the records in a fixed order.  No floating-point atomics, no second launch, no host sync: every
 // sum has a fixed order, so the results are bit-reproducible run to run and under HIP-graph replay.
 //
-// This header is the one place where that protocol is spelled out.  Its users: edge_loss.hip (forward_tail: per (scale, sample), then per
-// launch), edge_loss_kinds.hip (forward_tail: per sample, then per launch), supervised_loss.hip (sup_fwd_kernel: per launch) and norm_act.hip
+// This header is the one place where that protocol is spelled out.  Its users: edge_fast.hpp (forward_tail of every edge_loss.hip forward kernel: per (scale, sample),
+// then per launch), edge_loss_kinds.hip (forward_tail: per sample, then per launch), supervised_loss.hip (sup_fwd_kernel: per launch) and norm_act.hip
 // (gn_stats_kernel: per sample).  The fixed-order reductions themselves differ per kernel and stay with the kernels.
 //
 //   writer, the threads that hold a value:   handoff::publish(record + i, v);
@@ -41,7 +41,7 @@ __device__ __forceinline__ void publish(double* slot, double v) {
 __device__ __forceinline__ double read(const double* slot) { return __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // arrive = drain, then draw.  Both are called by EVERY thread of the workgroup, once its publish calls are issued.  A kernel that has
-// workgroup-wide work to place between the barrier and the ticket (edge_loss.hip reads its image's record count there) calls the two itself.
+// workgroup-wide work to place between the barrier and the ticket (forward_tail of edge_fast.hpp reads its image's record count there) calls the two itself.
 //
 // drain: every wave waits for its exchanges to come back, then the workgroup meets.
 __device__ __forceinline__ void drain() {

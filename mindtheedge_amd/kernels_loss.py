@@ -185,7 +185,7 @@ def _pair_raw(name, *args):
 class DepthLossesPairFn(torch.autograd.Function):
     """Every loss term of SemiSupEdgeCompletionModel.forward (models/SemiSupEdgeCompletionModel.py:128-165) in ONE forward and ONE backward
     launch: the depth-edge loss of all scales and, when `gt_depth` is given, the sparse silog loss of scale 0, for the RGB predictions
-    (branch 0) and the RGB+LiDAR predictions (branch 1) against the same labels, which are read once (csrc/edge_loss_pair.hip).
+    (branch 0) and the RGB+LiDAR predictions (branch 1) against the same labels, which are read once (the <2> instantiation of csrc/edge_fast.hpp, behind the pair entry points of csrc/edge_loss.hip).
     apply(weight, pos_to_neg, thresh, gt_depth, edges, normals, *preds_rgb, *preds_rgbd) -> fp32 [2, S (+1)]: per branch weight * balanced BCE
     per scale, then that branch's silog loss when gt_depth is given.  Where the library answers MTE_ERR_UNSUPPORTED (a scale outside the
     training configuration: no normals, W % 4 != 0, an unaligned base) the same numbers come from two DepthLossesFn applications."""

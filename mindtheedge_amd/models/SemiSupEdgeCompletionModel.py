@@ -20,7 +20,7 @@ here it raises a ValueError that names the missing key and the setting that prov
 
 In the shipped-like configuration (four scales, GradLoss('cross_entropy') head, 'sparse-silog' on one scale, labels at the predictions' sizes,
 no `rgb_edge` mask) all ten loss terms of a step -- 2 x 4 edge losses and 2 silog losses -- run as ONE forward and ONE backward launch that
-read the labels once (kernels.DepthLossesPairFn, csrc/edge_loss_pair.hip; ``fuse_losses``).  Every other configuration takes the per-scale
+read the labels once (kernels.DepthLossesPairFn, csrc/edge_fast.hpp; ``fuse_losses``).  Every other configuration takes the per-scale
 path of SemiSupEdgeModel, once per branch, on the existing kernels.  Eval mode is SfmModel.forward, unchanged.
 """
 from .SemiSupEdgeModel import SemiSupEdgeModel

@@ -1,12 +1,13 @@
 """GPU (-m gpu): depth completion training -- the two-branch one-launch loss (kernels.DepthLossesPairFn -> mte_edge_loss_pair_fwd / _bwd,
-csrc/edge_loss_pair.hip), the two completion models, one training step and the entry point.
+the <2> instantiation of csrc/edge_fast.hpp), the two completion models, one training step and the entry point.
 
 Pair path: the depth-edge loss of four scales + the silog loss of scale 0 for TWO sets of predictions against one set of labels, against
   * the float64 oracle (oracle/loss_oracle.py), losses 1e-4 and gradients 2e-4 of the largest gradient of a map (the single launch's bars);
-  * two single launches (kernels.DepthLossesFn) within 2e-6 / 2e-5, the bar between the fused and the per-scale path of the single launch;
+  * two single launches (kernels.DepthLossesFn), bit for bit: both are instantiations of one template with the same order of every sum;
   * itself: swapping the branches swaps the outputs bit for bit, a branch does not see the other one, repeated runs are bit-equal.
 Shapes: one tile; a 4 x 8 lowest scale (one partial tile); a partial last tile column with three consecutive tiles per workgroup; several
-tile rows with a partial lowest scale; B = 8, i.e. 64 (branch, scale, sample) images in the finish.
+tile rows with a partial lowest scale; B = 8, i.e. 64 (branch, scale, sample) images in the finish; B = 21 and 22, the last batch whose sums
+the finish stages in LDS and the first it reads straight from memory (one tile per image).
 Fallback: a width that is no multiple of 4 and a batch without normals answer MTE_ERR_UNSUPPORTED and run as two single launches."""
 import ctypes
 import functools
@@ -24,7 +25,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SFX = ["", "_1", "_2", "_3"]
 WEIGHT, POS_TO_NEG, THRESH = 10.0, 1.0, 4.0
-SHAPES = [(2, 64, 128), (1, 32, 64), (3, 96, 224), (2, 160, 320), (8, 32, 64)]
+SHAPES = [(2, 64, 128), (1, 32, 64), (3, 96, 224), (2, 160, 320), (8, 32, 64), (21, 32, 64), (22, 32, 64)]
 
 
 @functools.lru_cache(maxsize=None)
@@ -138,12 +139,12 @@ def test_pair_matches_two_single_launches(shape):
     a, b, batch = _maps(*shape)
     losses, grads = _pair(a, b, batch, True)
     gout = _gout(5)
-    bit_equal = True
     for br, invs in enumerate((a, b)):
         one, one_grads = _single(invs, batch, True, gout[br])
         _check(losses[br], grads[4 * br:4 * br + 4], one, one_grads, 2e-6, 2e-5)
-        bit_equal = bit_equal and torch.equal(losses[br], one) and all(torch.equal(x, y) for x, y in zip(grads[4 * br:4 * br + 4], one_grads))
-    print("pair == two single launches bit for bit:", bit_equal)
+        assert torch.equal(losses[br], one), br
+        for s, (x, y) in enumerate(zip(grads[4 * br:4 * br + 4], one_grads)):
+            assert torch.equal(x, y), (br, s)
 
 
 def test_branches_are_independent_and_swap_exactly():

@@ -84,9 +84,11 @@ def _close(got, want, tol, gtol):
         assert err <= gtol, (s, err)
 
 
-@pytest.mark.parametrize("shape", [(2, 64, 128), (1, 32, 64), (3, 96, 200), (2, 72, 100), (1, 40, 36), (2, 128, 320)])
+@pytest.mark.parametrize("shape", [(2, 64, 128), (1, 32, 64), (3, 96, 200), (2, 72, 100), (1, 40, 36), (2, 128, 320), (21, 32, 64), (22, 32, 64)])
 @pytest.mark.parametrize("normals", [True, False])
 def test_fused_losses_match_the_oracle_without_mask(shape, normals):
+    """B = 21 / 22 (one tile per image): the last batch whose sums the finish stages in LDS, and the first it reads straight from memory --
+    with normals in the training configuration's kernels, without in the generic ones."""
     B, H, W = shape
     invs, batch = _maps(B, H, W, seed=H + W + B, with_normals=normals)
     want = _oracle(invs, batch, None)
