@@ -202,7 +202,13 @@ int mte_gn_tail_fwd(const void* y1, long ld1, const double* stats1, const float*
                     int B, int HW, int C, float eps, int dtype, mte_stream_t stream);
 
 /* ---- 3-D packing / unpacking stencils: packing + nn.Conv3d(1,4,3,pad 1) (+ view / PixelShuffle)
- *      (layers01.py:127-149, 214-248 PackLayerConv3d; 251-287 UnpackLayerConv3d).  H,W,C describe x. */
+ *      (layers01.py:127-149, 214-248 PackLayerConv3d; 251-287 UnpackLayerConv3d).  H,W,C describe x.
+ * Rounding contract, every kernel form alike: w3 and b3 are fp32 and enter as they are (the matrix-core forms multiply with bf16(w) and
+ * bf16(w - bf16(w)), which together are w to 16 bits and exactly w for integers below 2^16); products and sums are fp32; out / dx are rounded
+ * ONCE, to nearest even, to the activation type; dwb[112] = (dw3[108], db3[4]) is fp32, cleared by the call and summed with float atomics.
+ * The one exception is not in the shipped library: the P3_ONE_BF16_WEIGHT forms of the development build (mte_debug_set(1, 300 + bits) with bit 4,
+ * csrc/p3_plan.hpp) multiply with bf16(w) alone -- each weight rounded once, to nearest even -- and are otherwise as above: their result is the
+ * operation on those rounded weights.  tests/test_gpu_conv3d_exact.py pins all of this bit for bit on integer operands. */
 int mte_pack3d_fwd(const void* x, long ldx, const float* w3, const float* b3, void* out, long ldo,
                    int B, int H, int W, int C, int dtype, mte_stream_t stream);
 int mte_pack3d_bwd_data(const void* dout, long ldo, const float* w3, void* dx, long lddx,

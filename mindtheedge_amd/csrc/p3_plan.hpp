@@ -25,6 +25,9 @@
 // pack forward and unpack forward as taps-in-K GEMMs, pack backward data as a banded GEMM, unpack backward data banded for C = 64 and by LDS-DMA with four
 // waves for C = 32, the conv3d weights split into bf16 hi + lo parts.  P3_UNPACK_FWD stays set but decides nothing there: the taps-in-K form comes first in
 // the ladder and takes every C the banded forward accepts.
+// Contract of P3_ONE_BF16_WEIGHT (HILO = false instances; development build only): each conv3d weight is rounded ONCE to bf16, to nearest even, and no lo part
+// is multiplied; products, sums and the store are as in every other form.  The result is the operation on the rounded weights, exactly
+// (tests/test_gpu_conv3d_exact.py checks it bit for bit), and differs from the hi + lo forms wherever w != bf16(w).
 enum : int {
     P3_UNPACK_BWD_DATA = 1,          // bit 0: unpack backward data as a banded GEMM (C = 32, 64)
     P3_UNPACK_BWD_DATA_DMA = 2,      // bit 1: ... by LDS-DMA of the raw records for C = 32

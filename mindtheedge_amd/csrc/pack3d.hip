@@ -839,6 +839,8 @@ __global__ __launch_bounds__(256) void unpack3d_bwd_data_lds4_kernel(P3LArgs a) 
 // 256 outputs = 4.5 cycles per output, with one LDS read per 2 MFMAs.  The banded operand is never stored: a lane's 8 entries are byte
 // permutes (v_perm_b32, selectors fixed per lane) of the two dwords {w0 w1} {w2 0} read from a 36-entry LDS table.
 // Operands are SWAPPED (weights first): an accumulator register then holds 4 consecutive DEPTHS of one pixel -> 8-byte stores.
+// HILO = false (P3_ONE_BF16_WEIGHT, csrc/p3_plan.hpp) leaves the lo MFMA out: the weights are then bf16(w), rounded once to nearest even, and the
+// result is the operation on THOSE weights -- inexact against fp32 weights by design, exact against the rounded ones (include/mte_kernels.h).
 //
 // unpack backward data, C = 32 / 64: tile = TH x 16 pixels, the four feature planes of the pixel-shuffled gradient staged together
 // ([plane][pixel][8 zero | C depths | 8 zero] bf16, 69 KB: two workgroups per CU); a wave owns 4 (tile row, depth block) units.
