@@ -440,6 +440,37 @@ int mte_canny_begin(const float* depth, int B, int H, int W, int n_pairs, const 
 int mte_resize_linear(const float* src, int B, int h, int w, float* dst, int H, int W, mte_stream_t stream);
 int mte_canny_propagate(unsigned char* state, int* flags, int sweeps, int maps, int H, int W, mte_stream_t stream);
 int mte_canny_finish(const unsigned char* state, float* edges, int maps, int H, int W, mte_stream_t stream);
+/* mte_canny_begin_fixed: the same pass at a FIXED scale, as edge_from_depth quantises (edge.py:73-93, the front end of
+ *   eval_depth_edges.py:264-280): vis = uint8(clamp(depth, min_depth, max_depth) * factor) with the caller's factor
+ *   (float32(255.0 / max_depth) upstream) instead of 255 / max(image); no max_ws.  n_pairs <= 12 (the twelve pairs
+ *   (t/2, t), t = 20 .. 240 of the benchmark in one pass).  Same state layout; propagate / finish as above. */
+int mte_canny_begin_fixed(const float* depth, int B, int H, int W, float min_depth, float max_depth, float factor, int n_pairs,
+                          const int* thresholds, unsigned char* vis_u8, unsigned char* state, mte_stream_t stream);
+
+/* ---- edge benchmark: pixel correspondence (eval_depth_edges.py:119-145,179-230: correspond_pixels.correspond_pixels of py-bsds500 with
+ * thresholds=1, apply_thinning=False).  PARITY UNPINNED against py-bsds500; exact against an independent maximum-matching solver.
+ * B instances, one workgroup each.  pred: float [B,H,W] and gt: float [Bg,H,W] edge images on the 0..255 scale (edge iff v/255 > 0.5);
+ * instance b is matched against gt[gt_of[b]] (DEVICE ints; twelve thresholds share one annotation).  Two pixels may be paired iff
+ * dx^2 + dy^2 <= r2, an integer the caller computes once in double: r2 = floor((max_dist * sqrt(H^2 + W^2))^2).
+ * result: int [B,4] = (matched, n_pred, n_gt, status); matched is the size of a MAXIMUM matching.  status 0 = ok, 1 = init_mate does not
+ * check out, 2 / 3 / 4 = the phase / level / path-walk bound was hit, 5 = queue overflow, 6 = gt_of[b] outside [0, Bg) -- with a non-zero
+ * status `matched` is not a maximum (0 for 1 and 6).  mate_pred (nullable): int [B,H,W], the linear index of each predicted pixel's
+ * partner or -1; the partners may differ between runs, the count may not.  init_mate (nullable): int [B,H,W], a matching to start from
+ * (-1 = none) instead of the greedy one; checked, not trusted: an entry on a pixel that is no predicted edge, a partner that is no
+ * ground-truth pixel, lies outside the image or outside r2, or is claimed twice gives status 1 for that instance and nothing else.
+ * MTE_ERR_UNSUPPORTED: r2 > 64 or H*W >= 2^30.  workspace: mte_edge_match_workspace_bytes(B,H,W,r2) bytes, needs no clearing. */
+long mte_edge_match_workspace_bytes(int B, int H, int W, int r2);
+int mte_edge_match(const float* pred, const float* gt, const int* gt_of, int B, int Bg, int H, int W, int r2, const int* init_mate,
+                   void* workspace, long workspace_bytes, int* result, int* mate_pred, mte_stream_t stream);
+
+/* ---- per-frame depth metrics of the analysis stage (eval_depth.py:348-410,432-456: DensePredictionAnalyzer.eval_frame).
+ * gt: DOUBLE [B,H,W] metres, pred: float [B,H,W].  mask = min_depth < gt < max_depth, inside columns [x0,x1) and rows [y0,y1)
+ * (clipped to the image like a numpy slice) or, with mask_u8 (nullable, [B,H,W] bytes), where mask_u8 > 0 (the crop is then unused).
+ * out: double [B,5] = mean_rel_err, std_rel_err (population), abs_rel_err, accuracy_1p1, accuracy_1p25; counts: long [B,3] = valid
+ * pixels and the two accuracy counts.  float64 arithmetic throughout with eps = 2^-52, sums in a fixed order (bit-reproducible); NaN
+ * in all of `out` when the mask is empty (np.nanmean).  One workgroup per frame, no workspace. */
+int mte_frame_depth_metrics(const double* gt, const float* pred, const unsigned char* mask_u8, int B, int H, int W,
+                            double min_depth, double max_depth, int x0, int x1, int y0, int y1, double* out, long* counts, mte_stream_t stream);
 
 /* ---- sparse auxiliary (SAN) branch.  PARITY UNPINNED: dense-equivalent of the
  * MinkowskiEngine operators the reference uses (networks/layers/minkowski_encoder.py:11-132, minkowski.py:33-79); see

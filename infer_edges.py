@@ -2,7 +2,14 @@
 """infer_edges.py -- depth inference core of the reference script (/root/reference/infer_edges.py:237-366, rows H3):
 image file -> PIL + LANCZOS resize -> [1,3,H,W] in [0,1] -> model_wrapper.depth(image)['inv_depths'][0][0] -> inv2depth ->
 ``NNNNNNNN_regular.npy`` (float32 metres) + ``NNNNNNNN_regular.png`` (depth / max * 255).
-The reference's BSDS / Canny evaluation around it is out of scope (py-bsds500, OpenCV)."""
+
+With an ``analysis`` section in the YAML the reference's analysis stage follows (infer_edges.py:129-183), on the device:
+``analysis.run_heavy_edge_metrics`` -> the edge benchmark over ``analysis.edge_image_list`` (mindtheedge_amd/utils/edge_benchmark.py) ->
+``sfm_analysis/debug_plots/edge_AUC.txt`` and ``mean_frames_bsds_edge_metrics.csv``; ``analysis.run_metrics`` -> the per-frame depth metrics
+against ``analysis.gt_image_list`` (utils/depth_analysis.py) -> ``frames_depth_metrics.csv`` and ``mean_frames_depth_metrics.csv``.
+``analysis.just_evaluate`` skips the inference and evaluates the ``*_regular.npy`` files already there.  Also read: ``analysis.min_depth``,
+``max_depth``, ``gt_crop``, ``eval_mask_image_list``, ``prec_recall_eval_range_min/max`` and ``save.folder`` (where predictions and analysis go
+when the analysis stage runs).  The plots, the pickle and the ordinal error are left out.  Without those keys nothing changes."""
 import argparse
 import os
 import sys
@@ -60,6 +67,45 @@ def save_depth(output_base, depth, png=True):
         Image.fromarray(np.clip(np.rint(d / d.max() * 255.0), 0, 255).astype(np.uint8)).save(output_base + '_regular.png')
 
 
+def _read_list(path):
+    with open(path) as f:
+        return [l.strip() for l in f.read().splitlines() if l.strip()]
+
+
+def run_analysis(config, folder):
+    """The reference's analysis stage (infer_edges.py:129-183) over the ``*_regular.npy`` predictions in ``folder``."""
+    import csv
+    import glob
+    import numpy as np
+    an = config.analysis
+    plots = os.path.join(folder, 'sfm_analysis', 'debug_plots')
+    os.makedirs(plots, exist_ok=True)
+    preds = sorted(glob.glob(os.path.join(folder, '*_regular.npy')))
+    lo = 0.0 if an.min_depth is None else float(an.min_depth)
+    hi = 80.0 if an.max_depth is None else float(an.max_depth)
+    crop = [44, 1197, 153, 371] if an.gt_crop is None else [int(v) for v in an.gt_crop]
+    if an.run_heavy_edge_metrics:
+        from mindtheedge_amd.utils.edge_benchmark import evaluate_lists
+        rmin = 0.12 if an.prec_recall_eval_range_min is None else float(an.prec_recall_eval_range_min)
+        rmax = 0.65 if an.prec_recall_eval_range_max is None else float(an.prec_recall_eval_range_max)
+        precision_vec, recall_vec, f1, f2 = evaluate_lists(preds, _read_list(an.edge_image_list), rmin, rmax,
+                                                           gt_crop=crop, min_depth=lo, max_depth=hi)
+        with open(os.path.join(plots, 'mean_frames_bsds_edge_metrics.csv'), 'w', newline='') as f:
+            w = csv.writer(f)
+            w.writerow(['', 'Precision', 'Recall'])
+            for i, (p, r) in enumerate(zip(precision_vec, recall_vec)):
+                w.writerow([i, p, r])
+        print('AUC over all range: ' + str(f1))
+        print('AUC over partial range: ' + str(f2))
+        with open(os.path.join(plots, 'edge_AUC.txt'), 'w') as f:
+            f.write('AUC over all range: ' + str(f1) + '\n')
+            f.write('AUC over partial range: ' + str(f2) + '\n')
+    if an.run_metrics:
+        from mindtheedge_amd.utils.depth_analysis import run_depth_metrics
+        masks = _read_list(an.eval_mask_image_list) if an.eval_mask_image_list else None
+        run_depth_metrics(_read_list(an.gt_image_list), preds, plots, lo, hi, gt_crop=crop, mask_list=masks)
+
+
 def main():
     ap = argparse.ArgumentParser(description='PackNet-SAN depth inference on MI355X')
     ap.add_argument('--config', type=str, required=True, help='YAML (model.depth_net.checkpoint_path may name a .ckpt)')
@@ -75,6 +121,13 @@ def main():
     from mindtheedge_amd.utils.config import load_config
     from mindtheedge_amd.models.model_wrapper import ModelWrapper
     config = load_config(args.config)
+    an = config.analysis or {}
+    analyse = bool(an.get('run_heavy_edge_metrics') or an.get('run_metrics'))
+    if analyse and (config.save or {}).get('folder'):
+        args.output = config.save.folder
+    if analyse and an.get('just_evaluate'):
+        run_analysis(config, args.output)
+        return
     if not os.path.exists(config.model.depth_net.checkpoint_path or ''):
         config.model.depth_net.checkpoint_path = ''
     wrapper = ModelWrapper(config).cuda()
@@ -99,6 +152,8 @@ def main():
             depth = infer_depth(wrapper, frame)
         save_depth(os.path.join(args.output, '%08d' % ctr), depth[0, 0], png=not args.no_png)
     print('wrote %d depth maps to %s' % (len(images), args.output))
+    if analyse:
+        run_analysis(config, args.output)
 
 
 if __name__ == '__main__':

@@ -19,7 +19,10 @@ constexpr int UW = TX + 4, UH = TY + 4;       // uint8 tile with a 2-pixel halo
 constexpr int MW = TX + 2, MH = TY + 2;       // magnitude tile with a 1-pixel halo
 constexpr int TG22 = 13573;                   // round(tan(22.5 deg) * 2^15)
 
-struct Pairs { int n; int low[4]; int high[4]; };
+constexpr int MAX_PAIRS = 12;                 // mte_canny_begin takes 4, the fixed-scale entry all twelve of the edge benchmark
+struct Pairs { int n; int low[MAX_PAIRS]; int high[MAX_PAIRS]; };
+// quantisation: 255 / max(image) (model_wrapper.py:396) or, fixed, clamp to [lo, hi] and the caller's factor (edge.py:81-87)
+struct Scale { int fixed; float lo, hi, factor; };
 
 __global__ __launch_bounds__(256) void image_max_kernel(const float* __restrict__ depth, unsigned* __restrict__ maxbits, int n) {
     const int b = blockIdx.y;
@@ -36,16 +39,18 @@ __global__ __launch_bounds__(256) void image_max_kernel(const float* __restrict_
 // state[pair][b][H][W]: 0 not an edge, 1 candidate, 2 edge
 __global__ __launch_bounds__(256) void canny_nms_kernel(const float* __restrict__ depth, const unsigned* __restrict__ maxbits,
                                                         unsigned char* __restrict__ vis, unsigned char* __restrict__ state,
-                                                        int B, int H, int W, Pairs pr) {
+                                                        int B, int H, int W, Pairs pr, Scale sc) {
     __shared__ int su[UH * UW];
     __shared__ int sdx[MH * MW], sdy[MH * MW], smag[MH * MW];
     const int b = blockIdx.z, x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
-    const float factor = 255.0f / __uint_as_float(maxbits[b]);
+    const float factor = sc.fixed ? sc.factor : 255.0f / __uint_as_float(maxbits[b]);
     const float* img = depth + (long)b * H * W;
     for (int i = threadIdx.x; i < UH * UW; i += 256) {
         const int ly = i / UW, lx = i % UW;
         const int gy = min(max(y0 + ly - 2, 0), H - 1), gx = min(max(x0 + lx - 2, 0), W - 1);      // BORDER_REPLICATE
-        su[i] = (int)(unsigned char)(int)(img[(long)gy * W + gx] * factor);
+        float v = img[(long)gy * W + gx];
+        if (sc.fixed) { if (v < sc.lo) v = sc.lo; if (v > sc.hi) v = sc.hi; }                        // NaN stays, as depth[depth < lo] = lo leaves it
+        su[i] = (int)(unsigned char)(int)(v * factor);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < MH * MW; i += 256) {
@@ -124,7 +129,22 @@ extern "C" int mte_canny_begin(const float* depth, int B, int H, int W, int n_pa
     if (mte_memset_async(max_ws, 0, sizeof(unsigned) * B, stream) != hipSuccess) return MTE_ERR_LAUNCH;
     int bx = cdiv((long)H * W, 256 * 8); if (bx > 256) bx = 256;
     hipLaunchKernelGGL(image_max_kernel, dim3(bx, B), dim3(256), 0, stream, depth, max_ws, H * W);
-    hipLaunchKernelGGL(canny_nms_kernel, dim3(cdiv(W, TX), cdiv(H, TY), B), dim3(256), 0, stream, depth, max_ws, vis_u8, state, B, H, W, pr);
+    hipLaunchKernelGGL(canny_nms_kernel, dim3(cdiv(W, TX), cdiv(H, TY), B), dim3(256), 0, stream, depth, max_ws, vis_u8, state, B, H, W, pr, Scale{0, 0.f, 0.f, 0.f});
+    return mte_check_launch();
+}
+
+extern "C" int mte_canny_begin_fixed(const float* depth, int B, int H, int W, float min_depth, float max_depth, float factor, int n_pairs,
+                                     const int* thresholds, unsigned char* vis_u8, unsigned char* state, hipStream_t stream) {
+    if (!depth || !thresholds || !state || B <= 0 || H <= 0 || W <= 0 || n_pairs < 1 || n_pairs > MAX_PAIRS || (long)H * W >= (1L << 30))
+        return MTE_ERR_ARG;
+    Pairs pr{};
+    pr.n = n_pairs;
+    for (int p = 0; p < n_pairs; ++p) {
+        pr.low[p] = thresholds[2 * p] < thresholds[2 * p + 1] ? thresholds[2 * p] : thresholds[2 * p + 1];
+        pr.high[p] = thresholds[2 * p] < thresholds[2 * p + 1] ? thresholds[2 * p + 1] : thresholds[2 * p];
+    }
+    hipLaunchKernelGGL(canny_nms_kernel, dim3(cdiv(W, TX), cdiv(H, TY), B), dim3(256), 0, stream, depth, (const unsigned*)nullptr, vis_u8, state, B, H, W, pr,
+                       Scale{1, min_depth, max_depth, factor});
     return mte_check_launch();
 }
 

@@ -220,6 +220,73 @@ __global__ __launch_bounds__(256) void post_process_kernel(const float* __restri
     out[i] = mh * a + m * hat + (1.f - m - mh) * fused;
 }
 
+
+// ---- per-frame metrics of the analysis stage (eval_depth.py:348-410,432-456).  One workgroup per frame, float64 throughout, two passes
+// (mean, then squared deviations, as np.nanstd takes them); every sum is taken in one fixed order: thread-strided, xor butterfly, 16 waves in turn.
+constexpr int FM_NT = 1024;
+
+struct FrameArgs {
+    const double* gt; const float* pred; const unsigned char* mask;
+    int H, W, x0, x1, y0, y1;
+    double lo, hi;
+};
+
+__device__ __forceinline__ double block_sum_d(double v, double* sred) {
+    v = wave_sum_d(v);
+    __syncthreads();                                      // sred may still be read from the previous call
+    if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = v;
+    __syncthreads();
+    double r = 0.0;
+    for (int w = 0; w < FM_NT / 64; ++w) r += sred[w];
+    return r;
+}
+
+__device__ __forceinline__ bool frame_valid(const FrameArgs& a, long base, int i, double& g) {
+    g = a.gt[base + i];
+    if (!(g > a.lo && g < a.hi)) return false;
+    if (a.mask) return a.mask[base + i] > 0;
+    const int y = i / a.W, x = i - y * a.W;
+    return x >= a.x0 && x < a.x1 && y >= a.y0 && y < a.y1;
+}
+
+__global__ __launch_bounds__(FM_NT) void frame_metrics_kernel(FrameArgs a, double* __restrict__ out, long* __restrict__ counts) {
+    __shared__ double sred[FM_NT / 64];
+    const int b = blockIdx.x, n = a.H * a.W;
+    const long base = (long)b * n;
+    const double eps = 2.220446049250313e-16;             // np.finfo(float).eps = 2^-52
+    double s_rel = 0.0, s_abs = 0.0, c = 0.0, c11 = 0.0, c125 = 0.0;
+    for (int i = threadIdx.x; i < n; i += FM_NT) {
+        double g;
+        if (!frame_valid(a, base, i, g)) continue;
+        const double d = (double)a.pred[base + i];
+        const double rel = (d - g) / (g + eps);
+        const double dev = fmax(fabs(d / (g + eps)), fabs(g / (d + eps)));
+        s_rel += rel; s_abs += fabs(rel); c += 1.0;
+        c11 += dev < 1.1 ? 1.0 : 0.0;
+        c125 += dev < 1.25 ? 1.0 : 0.0;
+    }
+    s_rel = block_sum_d(s_rel, sred);
+    s_abs = block_sum_d(s_abs, sred);
+    c = block_sum_d(c, sred);
+    c11 = block_sum_d(c11, sred);
+    c125 = block_sum_d(c125, sred);
+    const double mean = s_rel / c;                        // 0 / 0 = NaN for an empty mask, as np.nanmean
+    double s_dev = 0.0;
+    for (int i = threadIdx.x; i < n; i += FM_NT) {
+        double g;
+        if (!frame_valid(a, base, i, g)) continue;
+        const double t = ((double)a.pred[base + i] - g) / (g + eps) - mean;
+        s_dev += t * t;
+    }
+    s_dev = block_sum_d(s_dev, sred);
+    if (threadIdx.x == 0) {
+        double* o = out + 5 * (long)b;
+        o[0] = mean; o[1] = sqrt(s_dev / c); o[2] = s_abs / c; o[3] = c11 / c; o[4] = c125 / c;
+        long* k = counts + 3 * (long)b;
+        k[0] = (long)c; k[1] = (long)c11; k[2] = (long)c125;
+    }
+}
+
 }  // namespace
 
 extern "C" long mte_depth_metrics_workspace_bytes(int B) { return (long)B * WS_IMAGE_BYTES; }
@@ -268,5 +335,17 @@ extern "C" int mte_post_process_inv_depth(const float* inv_depth, const float* i
     if (method < 0 || method > 2) return MTE_ERR_UNSUPPORTED;
     const long rows = (long)B * H;
     hipLaunchKernelGGL(post_process_kernel, dim3(cdiv(rows * W, 256)), dim3(256), 0, stream, inv_depth, inv_depth_flipped, out, rows, W, method);
+    return mte_check_launch();
+}
+
+extern "C" int mte_frame_depth_metrics(const double* gt, const float* pred, const unsigned char* mask_u8, int B, int H, int W,
+                                       double min_depth, double max_depth, int x0, int x1, int y0, int y1, double* out, long* counts,
+                                       hipStream_t stream) {
+    if (!gt || !pred || !out || !counts || B <= 0 || H <= 0 || W <= 0 || (long)H * W >= (1L << 30)) return MTE_ERR_ARG;
+    FrameArgs a;
+    a.gt = gt; a.pred = pred; a.mask = mask_u8; a.H = H; a.W = W; a.lo = min_depth; a.hi = max_depth;
+    auto clip = [](int v, int n) { if (v < 0) v += n; return v < 0 ? 0 : v > n ? n : v; };          // a numpy slice bound
+    a.x0 = clip(x0, W); a.x1 = clip(x1, W); a.y0 = clip(y0, H); a.y1 = clip(y1, H);
+    hipLaunchKernelGGL(frame_metrics_kernel, dim3((unsigned)B), dim3(FM_NT), 0, stream, a, out, counts);
     return mte_check_launch();
 }
