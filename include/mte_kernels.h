@@ -532,6 +532,16 @@ int mte_edge_target_from_u8(const unsigned char* src, float* dst, long n, mte_st
 int mte_normal_target_from_u8(const unsigned char* src, float* dst, long n, mte_stream_t stream);
 int mte_resize_depth_preserve(const float* src, int B, int h, int w, float* dst, int H, int W, int* winner_ws, mte_stream_t stream);
 
+/* ---- evaluation-sample preparation (datasets/transforms.py:53-125).  PARITY UNPINNED restatements of OpenCV, like mte_resize_linear:
+ * mte_resize_linear_u8:   cv2.resize(uint8 [B,h,w] -> [B,H,W]) with the default INTER_LINEAR: per axis f = float((d+0.5)*(double(n)/N) - 0.5),
+ *   s = floor(f), f -= s, clamped to [0, n-1] with f = 0 at either end; coefficients rint(f*2048), rint((1.f-f)*2048) as 16-bit integers;
+ *   horizontal pass in int32, then dst = (((b0*(R0>>4))>>16) + ((b1*(R1>>4))>>16) + 2) >> 2.  With h == 2H and w == 2W exactly it is the
+ *   2x2 area average (sum + 2) >> 2 instead, as OpenCV switches.  No workspace: each output pixel recomputes its two row taps.
+ * mte_resize_nearest_f32: cv2.resize(float32 [B,h,w] -> [B,H,W], INTER_NEAREST): sx = min(floor(dx * (1.0/(double(W)/w))), w-1), rows alike.
+ * Null pointers, non-positive sizes, B > 65535 or a map of 2^30 pixels or more return MTE_ERR_ARG and launch nothing. */
+int mte_resize_linear_u8(const unsigned char* src, int B, int h, int w, unsigned char* dst, int H, int W, mte_stream_t stream);
+int mte_resize_nearest_f32(const float* src, int B, int h, int w, float* dst, int H, int W, mte_stream_t stream);
+
 /* ---- training-image preparation (the 8-bit image half of datasets/transforms.py:17-50), bit for bit as PIL computes it
  * mte_image_resample_u8: Image.crop + Image.resize((out_w, out_h), LANCZOS) of an 8-bit RGB frame (HWC): PIL's ImagingResample, horizontal
  *   pass then vertical pass, each clipped to uint8.  src / src_stride (bytes) describe the whole frame, (crop_x, crop_y, in_w, in_h) the

@@ -153,12 +153,21 @@ class KittiEdgeSplitDataset:
 
     input_depth_type (None, '' or [''] = off) switches the split's LiDAR column on (.png / .npy / velodyne .bin, lidar_prep.py): cropped
     and resized like the depth map it becomes ``lidar`` and ``input_depth``; with lidar_scale and lidar_add both non-empty (2 x 3 ranges,
-    reference augment_depth_values) the ``input_depth`` copy is perturbed with lidar_drop_rate, drawing from ``np.random``."""
+    reference augment_depth_values) the ``input_depth`` copy is perturbed with lidar_drop_rate, drawing from ``np.random``.
+
+    mode 'validation' / 'test' (default 'train') returns the reference's validation_transforms / test_transforms sample instead
+    (datasets/eval_prep.py): crop_eval_borders crops rgb, input_depth and rgb_edge only, validation takes its size from the frame, test
+    resizes to image_shape when one is given (() = not at all); depth keeps its native size; no jitter, no perturbation, no normals."""
 
     def __init__(self, split_file, image_shape, device='cuda', root='', jittering=(), crop_train_borders=(), input_depth_type=None,
-                 lidar_scale=(), lidar_add=(), lidar_drop_rate=0.0):
+                 lidar_scale=(), lidar_add=(), lidar_drop_rate=0.0, mode='train', crop_eval_borders=()):
+        if mode not in ('train', 'validation', 'test'):
+            raise ValueError("Unknown mode {}".format(mode))
+        self.mode = mode
+        self.crop_eval_borders = tuple(crop_eval_borders or ())
         self.records = read_split(split_file)
-        self.shape = (int(image_shape[0]), int(image_shape[1]))
+        # the evaluation modes take their size from the frame (validation) or resize only when a shape is given (test)
+        self.shape = (int(image_shape[0]), int(image_shape[1])) if image_shape is not None and len(image_shape) > 0 else ()
         self.device = torch.device(device)
         self.root = root
         self.jittering = tuple(jittering or ())
@@ -181,7 +190,41 @@ class KittiEdgeSplitDataset:
             a = a[borders[1]:borders[3], borders[0]:borders[2]]               # crop_depth, augmentations.py:425-444
         return torch.from_numpy(np.ascontiguousarray(a).astype(np.uint8)).to(self.device)
 
+    def _map(self, path):
+        """an annotation map as its file holds it: uint8 (PNG) or float32 (.npy), on the device"""
+        import numpy as np
+        a = _read_gray_u8(path)
+        a = a.astype(np.uint8) if a.dtype.kind in 'ub' else a.astype(np.float32)
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
+    def _eval_item(self, idx):
+        """mode 'validation' / 'test': the files decoded on the host as in training, then eval_prep.validation_sample / test_sample on the
+        device (the reference's validation_transforms / test_transforms, datasets/transforms.py:53-125)."""
+        import numpy as np
+        from PIL import Image
+        from . import eval_prep as ep
+        rec = self.records[idx]
+        img = Image.open(self._p(rec['rgb'])).convert('RGB')
+        sample = {'idx': idx, 'rgb': torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(self.device)}
+        d_full = None
+        if rec.get('depth'):
+            d_full = read_png_depth(self._p(rec['depth']))
+            sample['depth'] = torch.from_numpy(d_full).to(self.device)
+        if self.with_input_depth and rec.get('lidar'):
+            from . import lidar_prep as lp
+            sample['input_depth'] = lp.read_lidar_map(self._p(rec['lidar']), self.device, depth_map=d_full)
+        if rec.get('edge'):
+            for s, p in enumerate(multiscale_paths(self._p(rec['edge']))):
+                sample['edge' if s == 0 else 'edge_%d' % s] = self._map(p)
+        if rec.get('rgb_edge'):
+            sample['rgb_edge'] = self._map(self._p(rec['rgb_edge']))
+        if self.mode == 'validation':
+            return ep.validation_sample(sample, self.crop_eval_borders)
+        return ep.test_sample(sample, self.shape, self.crop_eval_borders)
+
     def __getitem__(self, idx):
+        if self.mode != 'train':
+            return self._eval_item(idx)
         import numpy as np
         from PIL import Image
         from . import image_prep as ip
@@ -278,3 +321,75 @@ def make_loader(config, rank, world):
                                input_depth_type=tr.get('input_depth_type'), lidar_scale=_as_tuple(aug.get('lidar_scale')),
                                lidar_add=_as_tuple(aug.get('lidar_add')), lidar_drop_rate=float(aug.get('lidar_drop_rate') or 0.0))
     return SplitLoader(ds, int(tr.batch_size), rank, world)
+
+
+# ---- evaluation loaders (reference setup_dataset / setup_dataloader, models/model_wrapper.py:675-790) ---------------------------------
+
+def shard_indices(n, rank, world):
+    """The frames of rank ``rank``: r, r + world, ... in file order, nothing padded.  The reference's DistributedSampler repeats frames to
+    even the ranks out and all_reduce_metrics removes the repeats by 'idx'; here every frame is seen exactly once and
+    ModelWrapper.validation_epoch_end divides the summed metrics by the summed count."""
+    return list(range(int(n)))[int(rank)::int(world)]
+
+
+class EvalLoader:
+    """File order, rank-strided (shard_indices), keeps the ragged tail.  Frames of one batch must share their sizes."""
+
+    def __init__(self, dataset, batch_size=1, rank=0, world=1):
+        self.ds, self.bs, self.rank, self.world = dataset, max(int(batch_size), 1), rank, world
+
+    def indices(self):
+        return shard_indices(len(self.ds), self.rank, self.world)
+
+    def __len__(self):
+        return (len(self.indices()) + self.bs - 1) // self.bs
+
+    def __iter__(self):
+        mine = self.indices()
+        for i in range(0, len(mine), self.bs):
+            samples = [self.ds[j] for j in mine[i:i + self.bs]]
+            for s in samples[1:]:
+                for k, v in s.items():
+                    if torch.is_tensor(v) and tuple(v.shape) != tuple(samples[0][k].shape):
+                        raise ValueError("batch_size {} needs frames of one size: '{}' is {} in frame {} and {} in frame {}".format(
+                            self.bs, k, tuple(samples[0][k].shape), samples[0]['idx'], tuple(v.shape), s['idx']))
+            yield collate(samples)
+
+
+def _at(values, i, default=''):
+    """entry i of a per-dataset list of the config; a scalar or a one-entry list counts for every dataset (default_config.py: [''])"""
+    if not isinstance(values, (list, tuple)):
+        return default if values is None else values
+    if len(values) == 0:
+        return default
+    return values[i] if i < len(values) else values[-1]
+
+
+def _make_eval_loaders(config, mode, rank, world):
+    section = config.datasets[mode]
+    splits = section.get('split') or []
+    splits = [splits] if isinstance(splits, str) else list(splits)
+    aug = config.datasets.augmentation
+    shape = aug.get('image_shape')
+    shape = _as_tuple(shape)
+    loaders = []
+    for i, split in enumerate(splits):
+        name = _at(section.get('dataset'), i, 'KITTI')
+        if name not in ('KITTI', 'GTA'):                                  # both are the 8-column split reader (model_wrapper.py:700-735)
+            raise ValueError("Unknown dataset {} (KITTI and GTA read the 8-column split file)".format(name))
+        root = _at(section.get('path'), i, '')
+        split_file = split if os.path.isabs(split) or os.path.exists(split) or not root else os.path.join(root, split)
+        ds = KittiEdgeSplitDataset(split_file, shape, device=torch.device('cuda', torch.cuda.current_device()), root=root,
+                                   input_depth_type=_at(section.get('input_depth_type'), i, ''), mode=mode,
+                                   crop_eval_borders=_as_tuple(aug.get('crop_eval_borders')))
+        loaders.append(EvalLoader(ds, int(section.get('batch_size') or 1), rank, world))
+    return loaders
+
+
+def make_val_loaders(config, rank=0, world=1):
+    """One EvalLoader per entry of config.datasets.validation.split ([] without one); path / depth_type / input_depth_type per index."""
+    return _make_eval_loaders(config, 'validation', rank, world)
+
+
+def make_test_loaders(config, rank=0, world=1):
+    return _make_eval_loaders(config, 'test', rank, world)

@@ -2,7 +2,9 @@
 ``setup_depth_net``, ``setup_depth_edge_loss`` (:561-672), ``configure_optimizers`` (:142-180), ``training_step``
 (:197-213), ``depth`` (:318-321), and the depth half of validation: ``evaluate_depth`` (:328-352), ``validation_step``
 (:215-225), ``validation_epoch_end`` (:255-277) with the metrics computed on the device.
-Dataloaders, metric printing and the Canny/chamfer edge metrics (OpenCV) are out of scope."""
+With config.datasets.validation.path / split set the metric keys carry the reference's dataset prefix (``dataset_prefix``) and rank 0
+prints one line per dataset and epoch; ``test_step`` / ``test_epoch_end`` give the depth metrics of a test split.  The loaders themselves
+are datasets/kitti_edges.py::make_loader / make_val_loaders / make_test_loaders; wandb logging and save_depth are not rebuilt."""
 import random
 from collections import OrderedDict
 
@@ -158,23 +160,84 @@ class ModelWrapper(nn.Module):
             # reference :354-371 + compute_edge_metrics :373-440: Canny on the FIRST image's predicted depth (three settings)
             # (resized to the edge image's size) against its ground-truth edge image -> (precision, recall, F1) x 3.  The
             # resize and Canny steps restate OpenCV's published algorithms and are parity-unpinned (oracle/canny_oracle.py);
-            # the chamfer part is pinned.
-            from ..utils.edge import compute_edge_metrics_from_depth
+            # the chamfer part is pinned.  The depth-edge estimators' output already is an edge probability: it is thresholded
+            # instead (:403-415).  datasets.validation.gt_crop[dataset_idx] restricts the scored window (:422-433).
+            from ..utils.edge import compute_edge_metrics_from_depth, compute_edge_metrics_from_probability
+            dataset_idx = int(args[1]) if args is not None and len(args) > 1 and args[1] is not None else 0
+            gt_crops = (self.config.datasets.get('validation') or {}).get('gt_crop') or []
+            gt_crop = gt_crops[dataset_idx] if len(gt_crops) > 0 else None
+            estimator = self.config.model.name.startswith(('EdgeEstimation', 'EdgeClassification'))
             gt_edge = batch['edge'][0, 0].float() * 255
-            metrics['edges'] = compute_edge_metrics_from_depth(depth[0, 0], gt_edge)
+
+            def edge_metrics(inv):
+                if estimator:
+                    return compute_edge_metrics_from_probability(inv[0, 0], gt_edge, gt_crop=gt_crop)
+                return compute_edge_metrics_from_depth(inv2depth(inv)[0, 0], gt_edge, gt_crop=gt_crop)
+            if estimator:
+                # the estimator MODEL halves the network's output (EdgeEstimationLIDARModel.forward); the reference thresholds the
+                # network's own RGB output, one more forward (:353-356)
+                metrics['edges'] = edge_metrics(self.depth(batch['rgb'], rgb_edge=batch.get('rgb_edge'))['inv_depths'][0][0][:, 0:1, :, :])
+            else:
+                metrics['edges'] = edge_metrics(inv_depth)
             if 'input_depth' in batch and getattr(self.model.depth_net, 'with_san', False):
                 # reference :357-368: the same metrics of the RGB+LiDAR prediction (the completion models validate both)
                 inv_input = self.depth(batch['rgb'], batch['input_depth'], rgb_edge=batch.get('rgb_edge'))['inv_depths'][0][0][:, 0:1, :, :]
-                metrics['edges_input'] = compute_edge_metrics_from_depth(inv2depth(inv_input)[0, 0], gt_edge)
+                metrics['edges_input'] = edge_metrics(inv_input)
         return {'metrics': metrics, 'inv_depth': inv_depth_pp}
 
     def validation_step(self, batch, *args):
         output = self.evaluate_depth(stack_batch(batch), args)
         return {'idx': batch.get('idx'), **output['metrics']}
 
-    def validation_epoch_end(self, output_data_batch):
-        """Mean of the per-batch metrics over the epoch (and over ranks) -> {'depth-abs_rel_pp_gt': float, ...}.
+    def dataset_prefix(self, mode, dataset_idx=0):
+        """The reference's metric prefix of dataset ``dataset_idx`` of config.datasets.<mode> (prepare_dataset_prefix, utils/logging.py:35-63):
+        the path's stem, then -<split stem>, -<depth_type> and -<camera> where given; None when the section names no path / split."""
+        import os
+        section = (self.config.datasets.get(mode) or {}) if self.config.get('datasets') else {}
+        paths, splits = section.get('path') or [], section.get('split') or []
+        if len(paths) <= dataset_idx or len(splits) <= dataset_idx:
+            return None
+        prefix = os.path.splitext(paths[dataset_idx].split('/')[-1])[0]
+        if splits[dataset_idx] != '' and '{' not in splits[dataset_idx]:
+            prefix += '-{}'.format(os.path.splitext(os.path.basename(splits[dataset_idx]))[0])
+        depth_types, cameras = section.get('depth_type') or [''], section.get('cameras') or [[]]
+        if len(depth_types) > dataset_idx and depth_types[dataset_idx] != '':
+            prefix += '-{}'.format(depth_types[dataset_idx])
+        if len(cameras) > dataset_idx and len(cameras[dataset_idx]) == 1:
+            prefix += '-{}'.format(cameras[dataset_idx][0])
+        return prefix
+
+    def test_step(self, batch, *args):
+        """reference :227-236 without save_depth: the depth metrics of one test batch"""
+        batch = stack_batch(batch)
+        output = self.evaluate_depth({k: v for k, v in batch.items() if k != 'edge'}, args)
+        return {'idx': batch.get('idx'), **output['metrics']}
+
+    def test_epoch_end(self, output_data_batch, dataset_idx=0):
+        """reference :294-311: the depth metrics only, under the test section's prefix"""
+        return self._epoch_end(output_data_batch, self.dataset_prefix('test', dataset_idx), edges=False)
+
+    def validation_epoch_end(self, output_data_batch, dataset_idx=0):
+        """Mean of the per-batch metrics over the epoch (and over ranks) -> {'depth-abs_rel_pp_gt': float, ...}; with
+        config.datasets.validation.path / split set the keys carry the reference's prefix instead (create_dict, utils/reduce.py:119-154):
+        '<prefix>-abs_rel_pp_gt', '<prefix>-precision_0' ('<prefix>-precision_0_input' for the RGB+LiDAR prediction, the reference's '_input' mode).
         One host read per epoch."""
+        prefix = self.dataset_prefix('validation', dataset_idx)
+        out = self._epoch_end(output_data_batch, prefix, edges=True)
+        import torch.distributed as dist
+        if prefix is not None and out and not (dist.is_available() and dist.is_initialized() and dist.get_rank() != 0):
+            self.print_metrics(out, prefix)
+        return out
+
+    def print_metrics(self, metrics, prefix):
+        """one line per dataset and epoch (reference :444-470 prints a table): the seven depth metrics in the four modes"""
+        parts = []
+        for mode in self.metrics_modes:
+            vals = ' '.join('{:.4f}'.format(metrics.get('{}-{}{}'.format(prefix, key, mode), float('nan'))) for key in self.metrics_keys)
+            parts.append('{}: {}'.format(mode.lstrip('_') or 'raw', vals))
+        print('validation epoch {} | {} | {} | {}'.format(self.current_epoch, prefix, ' '.join(self.metrics_keys), ' | '.join(parts)), flush=True)
+
+    def _epoch_end(self, output_data_batch, prefix, edges):
         import torch.distributed as dist
         names = [self.metrics_name + m for m in self.metrics_modes]
         rows = [torch.stack([o[n] for n in names]) for o in output_data_batch if all(n in o for n in names)]
@@ -189,10 +252,10 @@ class ModelWrapper(nn.Module):
         mean = (total / count).cpu()
         from .. import kernels as K
         K.check_device_errors()                              # the validation forwards of the epoch have finished (host read above)
-        out = {'{}-{}{}'.format(self.metrics_name, key, mode): float(mean[i, j])
+        out = {'{}-{}{}'.format(self.metrics_name if prefix is None else prefix, key, mode): float(mean[i, j])
                for i, mode in enumerate(self.metrics_modes) for j, key in enumerate(self.metrics_keys)}
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        for name in ('edges', 'edges_input'):                # 'edges_input': the RGB+LiDAR prediction's (evaluate_depth, reference :365-368)
+        for name in (('edges', 'edges_input') if edges else ()):     # 'edges_input': the RGB+LiDAR prediction's (evaluate_depth, reference :365-368)
             edge_rows = [o[name] for o in output_data_batch if name in o]
             if edge_rows or multi:                           # (precision, recall, F1) x the three Canny settings, reference :431-438
                 etotal = torch.stack(edge_rows).double().sum(0) if edge_rows else torch.zeros(9, dtype=torch.float64, device=dev)
@@ -204,7 +267,10 @@ class ModelWrapper(nn.Module):
                 emean = (etotal / ecount).cpu()
                 for k in range(emean.numel() // 3):
                     for j, key in enumerate(('precision', 'recall', 'f1')):
-                        out['{}-{}_{}'.format(name, key, k)] = float(emean[3 * k + j])
+                        if prefix is None:
+                            out['{}-{}_{}'.format(name, key, k)] = float(emean[3 * k + j])
+                        else:
+                            out['{}-{}_{}{}'.format(prefix, key, k, '_input' if name == 'edges_input' else '')] = float(emean[3 * k + j])
         return out
 
     def depth(self, *args, **kwargs):

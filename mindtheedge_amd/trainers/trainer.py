@@ -65,9 +65,13 @@ class Trainer:
                 history[-1]['validation'] = self.validate(val_dataloaders, module)
             # as the reference (:80-91): save BEFORE the epoch counter advances, so 'epoch' in the file is the 0-based index of
             # the epoch that just finished and a resume continues at epoch + 1 (one file per epoch, no top-k policy)
+            # a CheckpointPolicy (models/model_checkpoint.py) given as ``checkpoint`` decides from the epoch's validation metrics instead
             if self.checkpoint and self.is_rank_0:
-                from ..models.model_checkpoint import save_checkpoint
-                save_checkpoint(os.path.join(str(self.checkpoint), 'epoch={}.ckpt'.format(module.current_epoch)), module)
+                if hasattr(self.checkpoint, 'save'):
+                    self.checkpoint.save(module, history[-1].get('validation'))
+                else:
+                    from ..models.model_checkpoint import save_checkpoint
+                    save_checkpoint(os.path.join(str(self.checkpoint), 'epoch={}.ckpt'.format(module.current_epoch)), module)
             module.current_epoch += 1
             scheduler.step()
         return history
@@ -81,7 +85,7 @@ class Trainer:
         results = []
         for n, dataloader in enumerate(dataloaders):
             outputs = [module.validation_step(sample_to_cuda(batch, self.device), i, n) for i, batch in enumerate(dataloader)]
-            results.append(module.validation_epoch_end(outputs))
+            results.append(module.validation_epoch_end(outputs, n))
         module.train(was_training)
         return results
 

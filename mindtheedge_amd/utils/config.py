@@ -38,11 +38,17 @@ _DEFAULTS = {
     # jittering / crop_train_borders: () = off.  The reference's default_config.py:166 jitters with (0.2, 0.2, 0.2, 0.05) and crops
     # nothing; a run that wants the reference's recipe sets  datasets.augmentation.jittering: [0.2, 0.2, 0.2, 0.05]  in its YAML.
     # lidar_scale / lidar_add / lidar_drop_rate, input_depth_type, is_infer_rgb / is_infer_lidar: default_config.py:169-171,184,217,223-224
-    'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': (),
+    # validation / test sections, crop_eval_borders, gt_crop: default_config.py:168,192-225 (no validation split = no validation)
+    'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': (), 'crop_eval_borders': (),
                                   'lidar_scale': (), 'lidar_add': (), 'lidar_drop_rate': 0.0},
                  'train': {'batch_size': 8, 'input_depth_type': ['']},
-                 'test': {'input_depth_type': [''], 'is_infer_rgb': True, 'is_infer_lidar': True}},
-    'checkpoint': {'filepath': '', 'save_top_k': -1},
+                 'validation': {'batch_size': 1, 'dataset': [], 'path': [], 'split': [], 'depth_type': [''], 'input_depth_type': [''],
+                                'cameras': [[]], 'gt_crop': []},
+                 'test': {'batch_size': 1, 'dataset': [], 'path': [], 'split': [], 'depth_type': [''], 'cameras': [[]],
+                          'input_depth_type': [''], 'is_infer_rgb': True, 'is_infer_lidar': True}},
+    # monitor / monitor_index / mode: default_config.py:26-28.  save_top_k stays -1 here (the reference's default is 5): one file per epoch
+    # unless a config asks for the top-k policy (models/model_checkpoint.py::CheckpointPolicy)
+    'checkpoint': {'filepath': '', 'save_top_k': -1, 'monitor': 'loss', 'monitor_index': 0, 'mode': 'auto'},
 }
 
 

@@ -126,7 +126,7 @@ def resize_linear(img, shape):
     return out[0] if squeeze else out
 
 
-def compute_edge_metrics_from_depth(depth, gt_edge, edge_to_edge_thresh=5):
+def compute_edge_metrics_from_depth(depth, gt_edge, edge_to_edge_thresh=5, gt_crop=None):
     """ModelWrapper.compute_edge_metrics for depth models (model_wrapper.py:376-440) on ONE [H,W] depth map and its
     ground-truth edge image (0..255 scale): three Canny settings x (precision, recall, F1) -> float64 device tensor [9].
     The depth is first resized to the edge image's size like the reference does (cv2.resize, INTER_LINEAR).  The resize
@@ -136,4 +136,34 @@ def compute_edge_metrics_from_depth(depth, gt_edge, edge_to_edge_thresh=5):
     if depth.shape != gt_edge.shape:
         depth = resize_linear(depth, gt_edge.shape)
     edges = canny_from_depth(depth)
+    if gt_crop is not None and len(gt_crop) > 0:        # datasets.validation.gt_crop: Canny on the whole map, the window only is scored
+        return compute_edge_metrics([crop_to_gt_window(edges[p], gt_crop) for p in range(edges.shape[0])],
+                                    crop_to_gt_window(gt_edge, gt_crop), edge_to_edge_thresh)
     return compute_edge_metrics([edges[p] for p in range(edges.shape[0])], gt_edge, edge_to_edge_thresh)
+
+
+PROBABILITY_THRESHOLDS = (0.5, 0.75, 0.9)               # models/model_wrapper.py:413-415
+
+
+def crop_to_gt_window(image, gt_crop):
+    """image[..., c[2]:c[3], c[0]:c[1]] for gt_crop = [start_x, end_x, start_y, end_y] (model_wrapper.py:422-433); None / [] = whole image"""
+    if gt_crop is None or len(gt_crop) == 0:
+        return image
+    c = [int(v) for v in gt_crop]
+    return image[..., c[2]:c[3], c[0]:c[1]].contiguous()
+
+
+def compute_edge_metrics_from_probability(prob, gt_edge, edge_to_edge_thresh=5, gt_crop=None):
+    """ModelWrapper.compute_edge_metrics for the depth-edge estimators (model_wrapper.py:403-440) on ONE [H,W] edge-probability map (the
+    network's output as it is) and its ground-truth edge image (0..255 scale): the map is resized to the ground truth's size (cv2.resize,
+    INTER_LINEAR: the parity-unpinned resize_linear), thresholded at > 0.5, > 0.75 and > 0.9 into 0/255 maps, and each is scored against the
+    ground truth -> float64 device tensor [9] of (precision, recall, F1) x 3.  No host read."""
+    if prob.dim() != 2 or gt_edge.dim() != 2:
+        raise ValueError("one [H,W] probability map and one [H,W] edge image, as the reference evaluates them")
+    (p,), _ = _edge_maps(prob)
+    p = p[0]
+    if p.shape != gt_edge.shape:
+        p = resize_linear(p, gt_edge.shape)
+    gt = crop_to_gt_window(gt_edge.float(), gt_crop)
+    images = [crop_to_gt_window((p > t).to(torch.float32) * 255.0, gt_crop) for t in PROBABILITY_THRESHOLDS]
+    return compute_edge_metrics(images, gt, edge_to_edge_thresh)

@@ -3,7 +3,9 @@
 parse the YAML over the defaults, build ModelWrapper (registry -> SemiSupEdgeModel + PackNetSAN01 + GradLoss), fit.
 Multi-GPU: `python -m torch.distributed.run --nproc-per-node N train_edges.py <yaml>` (one process per GPU, RCCL).
 Datasets are outside this build's scope: `--synthetic` trains on synthetic frames of the
-configured image_shape; otherwise pass `--data module:callable` returning an iterable of batch dicts."""
+configured image_shape; otherwise pass `--data module:callable` returning an iterable of batch dicts.  With `--data` and a non-empty
+`datasets.validation.split` the validation loaders of datasets/kitti_edges.py::make_val_loaders run after every epoch (and before the
+first with `arch.validate_first`), and `checkpoint.save_top_k` / `monitor` / `mode` choose the files that `--save` keeps."""
 import argparse
 import importlib
 import os
@@ -22,7 +24,8 @@ def main():
     ap.add_argument('--epochs', type=int, default=1)
     ap.add_argument('--data', type=str, default=None)
     ap.add_argument('--resume', type=str, default=None, help='.ckpt in the reference layout (model_checkpoint.py:71-81) to resume from')
-    ap.add_argument('--save', type=str, default=None, help='write <save>/epoch=N.ckpt after every epoch (rank 0)')
+    ap.add_argument('--save', type=str, default=None, help='write <save>/epoch=N.ckpt after every epoch (rank 0); with checkpoint.save_top_k '
+                    'other than -1 and a validation split, the best k as epoch=N_<monitor>=<value>.ckpt')
     args = ap.parse_args()
     assert args.file.endswith('.yaml'), 'You need to provide a .yaml file'
     import torch
@@ -37,7 +40,9 @@ def main():
         config.model.depth_net.checkpoint_path = ''
     from mindtheedge_amd.models.model_checkpoint import load_checkpoint
     save_dir = args.save or (os.path.dirname(config.checkpoint.filepath) if config.checkpoint.filepath else None)
-    trainer = Trainer(**{**config.arch, 'checkpoint': save_dir})
+    from mindtheedge_amd.models.model_checkpoint import CheckpointPolicy
+    # save_top_k -1 (the default): <save>/epoch=N.ckpt every epoch; otherwise the best save_top_k by checkpoint.monitor of the validation
+    trainer = Trainer(**{**config.arch, 'checkpoint': CheckpointPolicy.from_config(save_dir, config.checkpoint) if save_dir else None})
     wrapper = ModelWrapper(config, resume=load_checkpoint(args.resume) if args.resume else None)
     import ast
     H, W = tuple(config.datasets.augmentation.image_shape) if not isinstance(config.datasets.augmentation.image_shape, str) \
@@ -49,7 +54,11 @@ def main():
         assert args.synthetic, 'no dataset: pass --synthetic or --data module:callable'
         loader = SyntheticLoader(config.datasets.train.batch_size, H, W, args.steps, trainer.device, trainer.proc_rank,
                                  lidar=args.synthetic_lidar)
-    wrapper.set_dataloaders(train=loader)
+    val_loaders = None
+    if args.data and config.datasets.validation.split:
+        from mindtheedge_amd.datasets.kitti_edges import make_val_loaders
+        val_loaders = make_val_loaders(config, trainer.proc_rank, trainer.world_size)
+    wrapper.set_dataloaders(train=loader, val=val_loaders)
     trainer.max_epochs = wrapper.current_epoch + args.epochs
     hist = trainer.fit(wrapper)
     if trainer.is_rank_0:
