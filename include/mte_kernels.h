@@ -593,6 +593,32 @@ int mte_lidar_scatter(int H, int W, int n, const unsigned char* keep, int n_keep
 int mte_lidar_project(const double* points, int N, const double* K, const float* depth_map, float* out, int H, int W, int* winner_ws,
                       mte_stream_t stream);
 
+/* ---- depth visualisation and ordinal error of the inference side (utils/depth.py:67-101 viz_inv_depth; infer_edges.py:355-366 the log
+ * colouring; utils/d3r.py), csrc/depth_viz.hip.  Every result is an integer or a copy of an input value: no floating-point atomics, results
+ * are bit-equal run to run.  Inputs are FINITE float32 (a NaN has no place in the order; it is not looked for).
+ * mte_order_stats_f32: image b = x[b * stride .. b * stride + n) (stride 0: the same image under several k); k = int [B] on the device.
+ *   out[b] = (the k[b]-th, the (k[b]+1)-th) smallest value, 0-based, both clamped to the last one; with positive_only (the reference's
+ *   filter_zeros) over the values > 0 only.  count_out (nullable): int [B], the number n' of values that took part (n, or those > 0); the
+ *   host reads it first where k depends on it.  n' = 0 gives (0, 0).  -0 is returned as +0.  Radix select, four 8-bit passes over the
+ *   order-preserving key, two launches each; work: mte_order_stats_work_bytes(B) bytes, 4-byte aligned, content on entry ignored.
+ *   B <= 65535; MTE_ERR_UNSUPPORTED for n >= 2^30.  np.percentile's interpolation between the two values is the host's (utils/depth.py).
+ * mte_colormap_u8: out uint8 [B,H,W,3] = table[idx], table = uint8 [256,3] on the device (the host quantises a float table by its caller's
+ *   rule: round-half-even for the cv2.imwrite path -- parity-unpinned against OpenCV's saturate_cast --, truncation for the log colouring),
+ *   idx = min(int(clip(t, 0, 1) * 256), 255) -- matplotlib's rule --, NaN -> (0, 0, 0).  lo_hi null: t = x / divisor[b] (IEEE float32
+ *   division).  lo_hi = float [B,2]: t = (float32(log(double(x))) - lo_hi[b][0]) / lo_hi[b][1] and divisor is not read.  A thread owns 4
+ *   pixels = 12 output bytes; `out` 4-byte aligned.  MTE_ERR_UNSUPPORTED for B*H*W >= 2^30.
+ * mte_d3r_count: gt, pred float32 [H,W]; index_work = the workspace mte_lidar_index(gt, H, W, ..) filled (the raster-order list of pixels
+ *   > 0), n = its count as read by the host; pairs = int [P,2] ordinals into that list.  *count (int, overwritten) = the number of pairs with
+ *   (g > 1 + 0.03 and p > float32(1 + 0.03)) or (g < 1 - 0.03 and p < float32(1 - 0.03)), g = the ratio of the two ground-truth values in
+ *   double, p = the ratio of the two predictions in float32.  A pair with an ordinal outside [0, n) counts as disagreeing. */
+long mte_order_stats_work_bytes(int B);
+int mte_order_stats_f32(const float* x, long stride, int B, long n, const int* k, int positive_only, float* out, int* count_out, void* work,
+                        mte_stream_t stream);
+int mte_colormap_u8(const float* x, int B, int H, int W, const float* divisor, const float* lo_hi, const unsigned char* table, unsigned char* out,
+                    mte_stream_t stream);
+int mte_d3r_count(const float* gt, const float* pred, int H, int W, const void* index_work, int n, const int* pairs, int P, int* count,
+                  mte_stream_t stream);
+
 #ifdef MTE_DEV
 /* Development knobs for same-box A/B measurements (tools/sweep.sh) and kernel-variant cross-checks (tests/).  NOT part of the
  * integration surface: exported only by libmte_hip_dev.so, the -DMTE_DEV build of the same sources (mindtheedge_amd/_build.py);

@@ -157,15 +157,18 @@ class KittiEdgeSplitDataset:
 
     mode 'validation' / 'test' (default 'train') returns the reference's validation_transforms / test_transforms sample instead
     (datasets/eval_prep.py): crop_eval_borders crops rgb, input_depth and rgb_edge only, validation takes its size from the frame, test
-    resizes to image_shape when one is given (() = not at all); depth keeps its native size; no jitter, no perturbation, no normals."""
+    resizes to image_shape when one is given (() = not at all); depth keeps its native size; no jitter, no perturbation, no normals.
+    with_filename (the config-driven loaders set it) adds the reference's ``filename = '<split stem>_%010d' % idx`` to these samples."""
 
     def __init__(self, split_file, image_shape, device='cuda', root='', jittering=(), crop_train_borders=(), input_depth_type=None,
-                 lidar_scale=(), lidar_add=(), lidar_drop_rate=0.0, mode='train', crop_eval_borders=()):
+                 lidar_scale=(), lidar_add=(), lidar_drop_rate=0.0, mode='train', crop_eval_borders=(), with_filename=False):
         if mode not in ('train', 'validation', 'test'):
             raise ValueError("Unknown mode {}".format(mode))
         self.mode = mode
         self.crop_eval_borders = tuple(crop_eval_borders or ())
         self.records = read_split(split_file)
+        self.split = split_file.split('/')[-1].split('.')[0]               # gta_dataset.py:149, the stem of the evaluation samples' 'filename'
+        self.with_filename = bool(with_filename)
         # the evaluation modes take their size from the frame (validation) or resize only when a shape is given (test)
         self.shape = (int(image_shape[0]), int(image_shape[1])) if image_shape is not None and len(image_shape) > 0 else ()
         self.device = torch.device(device)
@@ -206,6 +209,8 @@ class KittiEdgeSplitDataset:
         rec = self.records[idx]
         img = Image.open(self._p(rec['rgb'])).convert('RGB')
         sample = {'idx': idx, 'rgb': torch.from_numpy(np.asarray(img, dtype=np.uint8).copy()).to(self.device)}
+        if self.with_filename:
+            sample['filename'] = '%s_%010d' % (self.split, idx)            # gta_dataset.py:339: what save_depth names its files after
         d_full = None
         if rec.get('depth'):
             d_full = read_png_depth(self._p(rec['depth']))
@@ -381,7 +386,7 @@ def _make_eval_loaders(config, mode, rank, world):
         split_file = split if os.path.isabs(split) or os.path.exists(split) or not root else os.path.join(root, split)
         ds = KittiEdgeSplitDataset(split_file, shape, device=torch.device('cuda', torch.cuda.current_device()), root=root,
                                    input_depth_type=_at(section.get('input_depth_type'), i, ''), mode=mode,
-                                   crop_eval_borders=_as_tuple(aug.get('crop_eval_borders')))
+                                   crop_eval_borders=_as_tuple(aug.get('crop_eval_borders')), with_filename=True)
         loaders.append(EvalLoader(ds, int(section.get('batch_size') or 1), rank, world))
     return loaders
 

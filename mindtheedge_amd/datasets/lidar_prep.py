@@ -151,7 +151,8 @@ def project_lidar(points, K, shape=(1080, 1920), depth_map=None):
 
 def read_lidar_map(path, device, depth_map=None, clamp_negative=False):
     """One file of the split's LiDAR column -> float32 [h,w] on `device`: a 16-bit ``.png`` through read_png_depth (-1 = no return;
-    clamp_negative turns those into 0, as the annotation driver does), a ``.npy`` as it is, a velodyne ``.bin`` projected with the GTA
+    clamp_negative turns those into 0, as the annotation driver does), a ``.npy`` as it is, the ``velodyne_depth`` array of a ``.npz``
+    (infer_edges.py's split mode; clamped like the png), a velodyne ``.bin`` projected with the GTA
     intrinsics into the shape of depth_map (which then also removes returns that are off by more than 10 cm) or, without one, into the
     reference's 1080 x 1920."""
     from .kitti_edges import read_png_depth
@@ -168,8 +169,13 @@ def read_lidar_map(path, device, depth_map=None, clamp_negative=False):
             m[m < 0.0] = 0.0
     elif ext == 'npy':
         m = np.load(path)
+    elif ext == 'npz':                                                                 # read_npz_depth(file, 'velodyne'), kitti_dataset.py:35-38
+        with np.load(path) as z:
+            m = z['velodyne_depth'].astype(np.float32)
+        if clamp_negative:
+            m[m < 0.0] = 0.0
     else:
-        raise ValueError("LiDAR file {}: expected .png, .bin or .npy".format(path))
+        raise ValueError("LiDAR file {}: expected .png, .bin, .npy or .npz".format(path))
     if m.ndim != 2:
         raise ValueError("LiDAR file {} holds a {} array, expected [h,w]".format(path, m.shape))
     return torch.from_numpy(np.ascontiguousarray(m, dtype=np.float32)).to(device)

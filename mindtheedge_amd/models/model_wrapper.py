@@ -4,7 +4,7 @@
 (:215-225), ``validation_epoch_end`` (:255-277) with the metrics computed on the device.
 With config.datasets.validation.path / split set the metric keys carry the reference's dataset prefix (``dataset_prefix``) and rank 0
 prints one line per dataset and epoch; ``test_step`` / ``test_epoch_end`` give the depth metrics of a test split.  The loaders themselves
-are datasets/kitti_edges.py::make_loader / make_val_loaders / make_test_loaders; wandb logging and save_depth are not rebuilt."""
+are datasets/kitti_edges.py::make_loader / make_val_loaders / make_test_loaders; wandb logging is not rebuilt."""
 import random
 from collections import OrderedDict
 
@@ -208,9 +208,14 @@ class ModelWrapper(nn.Module):
         return prefix
 
     def test_step(self, batch, *args):
-        """reference :227-236 without save_depth: the depth metrics of one test batch"""
+        """reference :227-236: the depth metrics of one test batch; with config.save.folder set, save_depth (utils/save.py) writes the
+        sample's depth, RGB and colour files first"""
         batch = stack_batch(batch)
         output = self.evaluate_depth({k: v for k, v in batch.items() if k != 'edge'}, args)
+        save = self.config.get('save')
+        if save and save.get('folder'):
+            from ..utils.save import save_depth
+            save_depth(batch, output, args, self.config.datasets.test, save)
         return {'idx': batch.get('idx'), **output['metrics']}
 
     def test_epoch_end(self, output_data_batch, dataset_idx=0):

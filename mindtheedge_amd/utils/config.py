@@ -49,6 +49,8 @@ _DEFAULTS = {
     # monitor / monitor_index / mode: default_config.py:26-28.  save_top_k stays -1 here (the reference's default is 5): one file per epoch
     # unless a config asks for the top-k policy (models/model_checkpoint.py::CheckpointPolicy)
     'checkpoint': {'filepath': '', 'save_top_k': -1, 'monitor': 'loss', 'monitor_index': 0, 'mode': 'auto'},
+    # default_config.py:228-238: folder '' = ModelWrapper.test_step saves nothing (utils/save.py)
+    'save': {'folder': '', 'depth': {'rgb': True, 'viz': True, 'npz': True, 'png': True, 'multiscale': False}, 'pretrained': ''},
 }
 
 
