@@ -568,6 +568,30 @@ int mte_image_resample_u8(const unsigned char* src, long src_stride, int crop_x,
 int mte_color_jitter_u8_to_f32(const unsigned char* in, int B, int H, int W, const float* factors, const int* order, int any_contrast,
                                unsigned long long* luma_sums, float* out, float* out_original, mte_stream_t stream);
 
+/* ---- batched training-target preparation over a descriptor table (datasets/batch_prep.py, csrc/batch_prep.hip): what
+ * mte_resize_depth_preserve, the edge maps' conditional /255 and mte_normal_target_from_u8 do per map, for all maps of a batch in a fixed
+ * number of launches (one fill + three kernels, whatever n_maps is) and without a host read.
+ * arena: the batch's raw file contents on the device (arena_bytes bytes).  table: n_maps rows of MTE_BATCH_PREP_ROW_WORDS 64-bit integers
+ *   (kind, src_off, src_h, src_w, crop_x, crop_y, crop_h, crop_w, dst_off, dst_h, dst_w, 0): the source map is src_h x src_w elements of its
+ *   kind's type at byte src_off of the arena (aligned to that type), the crop window lies inside it, the result is dst_h x dst_w floats at
+ *   element dst_off of `out` (out_elems floats).  table_host and table_dev hold the SAME rows: the host copy is checked before anything is
+ *   launched (every offset, window and size; MTE_ERR_ARG otherwise), the kernels read the device copy.
+ * kinds: MTE_PREP_EDGE_U8    crop, preserve-resize of the pixels > 0 (target (int(y*H/h), int(x*W/w)) in double, last pixel in raster order
+ *                            wins, pixels that land outside are dropped), then x float32(1 / 255) if the maximum of the RESIZED map is > 1,
+ *                            decided per map on the device (the product, not the quotient: what `map / 255.0` of the per-sample path gives)
+ *        MTE_PREP_SPARSE_U16 16-bit depth: 0 = no return, otherwise float(v) / 256; crop, preserve-resize
+ *        MTE_PREP_SPARSE_F32 float depth as it is; crop, preserve-resize
+ *        MTE_PREP_NORMAL_U8  crop, (360 * (v / 255) - 180) * pi / 180 in double; the crop window must have the target's size
+ * work: winner_elems + n_maps ints of scratch, content on entry ignored; every map that is not MTE_PREP_NORMAL_U8 must end at or before
+ *   element winner_elems of `out` (lay the normals out last).  Integer atomics only: bit-reproducible. */
+#define MTE_PREP_EDGE_U8 0
+#define MTE_PREP_SPARSE_U16 1
+#define MTE_PREP_SPARSE_F32 2
+#define MTE_PREP_NORMAL_U8 3
+#define MTE_BATCH_PREP_ROW_WORDS 12
+int mte_batch_prep(const unsigned char* arena, long arena_bytes, const long* table_host, const long* table_dev, int n_maps, float* out,
+                   long out_elems, int* work, long winner_elems, mte_stream_t stream);
+
 /* ---- sparse LiDAR input (utils/depth.py:366-467 augment_depth_values; datasets/gta_dataset.py:85-104 process_lidar), csrc/lidar_prep.hip
  * Sparse maps are float32 [H,W] with 0 = no return, H * W < 2^30.  All arithmetic is double; results are rounded to float32 once, on the
  * final store.  The perturbation runs in three stages that share `work` (mte_lidar_perturb_work_bytes(H, W) bytes, 8-byte aligned, content

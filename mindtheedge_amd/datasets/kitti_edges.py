@@ -314,7 +314,9 @@ def make_loader(config, rank, world):
     """``train_edges.py --data mindtheedge_amd.datasets.kitti_edges:make_loader``: config.datasets.train.split[0] is the
     8-column split file, config.datasets.train.path[0] (optional) the root folder of its relative paths;
     config.datasets.augmentation.jittering / .crop_train_borders as in the reference (default (): off);
-    config.datasets.train.input_depth_type and config.datasets.augmentation.lidar_scale / lidar_add / lidar_drop_rate for the LiDAR column."""
+    config.datasets.train.input_depth_type and config.datasets.augmentation.lidar_scale / lidar_add / lidar_drop_rate for the LiDAR column.
+    config.datasets.train.num_workers (default 0) > 0 returns the prefetching loader (datasets/prefetch.py: same batches, decoded on that
+    many threads config.datasets.train.prefetch batches ahead) instead of SplitLoader."""
     tr = config.datasets.train
     shape = config.datasets.augmentation.image_shape
     shape = eval(shape) if isinstance(shape, str) else tuple(shape)
@@ -325,6 +327,10 @@ def make_loader(config, rank, world):
                                jittering=_as_tuple(aug.get('jittering')), crop_train_borders=_as_tuple(aug.get('crop_train_borders')),
                                input_depth_type=tr.get('input_depth_type'), lidar_scale=_as_tuple(aug.get('lidar_scale')),
                                lidar_add=_as_tuple(aug.get('lidar_add')), lidar_drop_rate=float(aug.get('lidar_drop_rate') or 0.0))
+    from .prefetch import PrefetchSplitLoader, choose_loader
+    if choose_loader(tr.get('num_workers')) == 'prefetch':
+        return PrefetchSplitLoader(ds, int(tr.batch_size), rank, world, num_workers=int(tr.get('num_workers')),
+                                   prefetch=int(tr.get('prefetch') or 2))
     return SplitLoader(ds, int(tr.batch_size), rank, world)
 
 

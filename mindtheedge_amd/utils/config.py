@@ -41,7 +41,10 @@ _DEFAULTS = {
     # validation / test sections, crop_eval_borders, gt_crop: default_config.py:168,192-225 (no validation split = no validation)
     'datasets': {'augmentation': {'image_shape': (384, 1280), 'jittering': (), 'crop_train_borders': (), 'crop_eval_borders': (),
                                   'lidar_scale': (), 'lidar_add': (), 'lidar_drop_rate': 0.0},
-                 'train': {'batch_size': 8, 'input_depth_type': ['']},
+                 # num_workers: 0 = SplitLoader (one sample at a time on the training stream).  The reference's default_config.py sets 16 DataLoader
+                 # processes; here > 0 selects the prefetching loader (datasets/prefetch.py) with that many decode THREADS (at most 16), `prefetch`
+                 # batches ahead; a run that wants it sets  datasets.train.num_workers: 8  in its YAML.
+                 'train': {'batch_size': 8, 'input_depth_type': [''], 'num_workers': 0, 'prefetch': 2},
                  'validation': {'batch_size': 1, 'dataset': [], 'path': [], 'split': [], 'depth_type': [''], 'input_depth_type': [''],
                                 'cameras': [[]], 'gt_crop': []},
                  'test': {'batch_size': 1, 'dataset': [], 'path': [], 'split': [], 'depth_type': [''], 'cameras': [[]],
