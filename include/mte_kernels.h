@@ -383,6 +383,23 @@ int mte_adam_step(float* p, const float* g, float* m, float* v, long n, float lr
  * so the training step can be replayed from a HIP graph (utils/graph.py::GraphedTrainStep) */
 int mte_adam_step_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
                       float gscale, mte_stream_t stream);
+/* ---- optimizer family (csrc/optim.hip): the other choices of config.model.optimizer, each one launch over the same flat buffers, each
+ * with a host-scalar form and a device-scalar form (graph replay) that give bit-equal results.  weight_decay >= 0.
+ * mte_adamw_step: decoupled = 0 is torch.optim.Adam(weight_decay) (g' = g * gscale + wd * p), decoupled = 1 torch.optim.AdamW
+ *   (p * (1 - lr * wd), taken as p - ((lr * wd) * p + update), lr * wd formed in the kernel); weight_decay = 0 equals mte_adam_step bit
+ *   for bit.  hyper as mte_adam_step_dev's.
+ * mte_sgd_step: torch.optim.SGD(momentum, dampening, weight_decay, nesterov).  momentum = 0 reads and writes no `buf` (null accepted);
+ *   with momentum, `buf` is zero before step 1.  The device form reads hyper = {lr, mu_eff, (1 - dampening)_eff}: {lr, 0, 1} at step 1
+ *   ("buf = g' on the first step"), {lr, momentum, 1 - dampening} afterwards; its `momentum` argument is the launch constant of
+ *   Nesterov's look-ahead.  nesterov needs momentum > 0 (and dampening = 0 in the host form), else MTE_ERR_ARG. */
+int mte_adamw_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps, float weight_decay,
+                   int decoupled, int step, float gscale, mte_stream_t stream);
+int mte_adamw_step_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                       float weight_decay, int decoupled, float gscale, mte_stream_t stream);
+int mte_sgd_step(float* p, const float* g, float* buf, long n, float lr, float momentum, float dampening, float weight_decay, int nesterov,
+                 int step, float gscale, mte_stream_t stream);
+int mte_sgd_step_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
+                     float gscale, mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

@@ -386,3 +386,19 @@ def adam_step_flat(p, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, gsca
     _K.lib.mte_adam_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(betas[0]), float(betas[1]),
                       float(eps), int(step), float(gscale), _K._stream())
     _K.bump_weights_epoch()
+
+
+def adamw_step_flat(p, g, m, v, step, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, decoupled=False, gscale=1.0):
+    """In-place fused Adam with weight decay over flat fp32 device buffers: torch.optim.Adam(weight_decay) or, decoupled, torch.optim.AdamW."""
+    _K._require_gpu(p)
+    _K.lib.mte_adamw_step(p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                          float(eps), float(weight_decay), int(bool(decoupled)), int(step), float(gscale), _K._stream())
+    _K.bump_weights_epoch()
+
+
+def sgd_step_flat(p, g, buf, step, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, gscale=1.0):
+    """In-place fused torch.optim.SGD over flat fp32 device buffers; ``buf`` (zero before step 1) may be None when momentum is 0."""
+    _K._require_gpu(p)
+    _K.lib.mte_sgd_step(p.data_ptr(), g.data_ptr(), None if buf is None else buf.data_ptr(), p.numel(), float(lr), float(momentum),
+                        float(dampening), float(weight_decay), int(bool(nesterov)), int(step), float(gscale), _K._stream())
+    _K.bump_weights_epoch()

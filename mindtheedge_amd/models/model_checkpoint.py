@@ -1,6 +1,6 @@
 """Checkpoint FORMAT of the reference (checkpoint half): packnet_sfm/models/model_checkpoint.py:71-81
 writes ``{'config', 'epoch', 'state_dict', 'optimizer', 'scheduler'}`` with ``state_dict`` keys ``model.depth_net.*`` and
-``torch.optim.Adam``'s optimizer layout; packnet_sfm/utils/load.py:117-201 reads it back (and TRI's published
+the optimizer layout of the configured torch class (``torch.optim.Adam`` / ``AdamW`` / ``SGD``); packnet_sfm/utils/load.py:117-201 reads it back (and TRI's published
 ``PackNetSAN01_*.ckpt`` files, whose extra sparse-branch tensors are skipped by the shape-checked, non-strict load in
 ``utils/load.py::load_network``).  ``save_checkpoint`` writes one file, ``load_checkpoint`` reads one; ``CheckpointPolicy`` is the
 keep-the-best-k part of the reference's ModelCheckpoint around them (its S3 sync, code tarball, F1 file-name suffix and save_freq
@@ -33,8 +33,9 @@ def save_checkpoint(filepath, model_wrapper):
         'scheduler': model_wrapper.scheduler.state_dict() if model_wrapper.scheduler is not None else None,
     }
     if ckpt['optimizer'] is not None:
-        for st in ckpt['optimizer']['state'].values():
-            st['exp_avg'], st['exp_avg_sq'] = st['exp_avg'].cpu(), st['exp_avg_sq'].cpu()
+        # every tensor of a state entry, whatever the optimizer keeps (Adam / AdamW: step, exp_avg, exp_avg_sq; SGD: momentum_buffer)
+        ckpt['optimizer']['state'] = {i: {k: v.cpu() if torch.is_tensor(v) else v for k, v in st.items()}
+                                      for i, st in ckpt['optimizer']['state'].items()}
     torch.save(ckpt, filepath)
     return filepath
 

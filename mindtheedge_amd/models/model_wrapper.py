@@ -91,20 +91,35 @@ class ModelWrapper(nn.Module):
         return self.current_epoch / self.config.arch.max_epochs
 
     def configure_optimizers(self, process_group=None):
-        """Adam over depth_net.parameters() (param group 'Depth') + StepLR, as the reference; the optimizer is the
-        fused flat Adam and carries the bucketed RCCL gradient averaging when torch.distributed is initialised."""
+        """config.model.optimizer.name ('Adam', 'AdamW' or 'SGD') over depth_net.parameters() (param group 'Depth') + StepLR, as the
+        reference: the keyword arguments are the keys of config.model.optimizer.depth that torch.optim.<name> accepts (filter_args), so
+        lr, weight_decay, betas, eps, momentum, dampening and nesterov work when a YAML names them.  The optimizer is the fused flat
+        one of that name and carries the bucketed RCCL gradient averaging when torch.distributed is initialised."""
         import torch.distributed as dist
-        from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, broadcast_parameters,
+        from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedSGD, broadcast_parameters,
                                               reference_parameter_names)
         opt_cfg = self.config.model.optimizer
-        if opt_cfg.name != 'Adam' or opt_cfg.depth.get('weight_decay', 0.0) not in (0, 0.0):
-            raise NotImplementedError("the shipped configs use Adam without weight decay")
+        built = {'Adam': FusedAdam, 'AdamW': FusedAdam, 'SGD': FusedSGD}
+        if opt_cfg.name not in built:
+            raise NotImplementedError("optimizer '{}' is not built: model.optimizer.name is one of {} (fused flat steps, "
+                                      "without amsgrad and maximize)".format(opt_cfg.name, sorted(built)))
+        kwargs = filter_args(getattr(torch.optim, opt_cfg.name), opt_cfg.depth)
+        for key in ('amsgrad', 'maximize'):
+            if kwargs.pop(key, False):
+                raise NotImplementedError("{}: true is not built: the fused {} steps are {} without amsgrad and maximize"
+                                          .format(key, opt_cfg.name, sorted(built)))
+        for key in ('params', 'foreach', 'capturable', 'differentiable', 'fused'):     # how torch would run its own step: no meaning here
+            kwargs.pop(key, None)
+        if opt_cfg.name == 'AdamW':
+            kwargs['decoupled_weight_decay'] = True
+        if 'betas' in kwargs:
+            kwargs['betas'] = tuple(kwargs['betas'])
         flat = FlatParameters(self.depth_net.parameters())
         reducer = None
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
             broadcast_parameters(flat, group=process_group)
             reducer = BucketedAllReduce(flat, process_group)
-        optimizer = FusedAdam(flat, lr=opt_cfg.depth.lr, reducer=reducer, name='Depth')
+        optimizer = built[opt_cfg.name](flat, reducer=reducer, name='Depth', **kwargs)
         optimizer.set_index_space(reference_parameter_names(self.depth_net), dict(self.depth_net.named_parameters()))
         sched = getattr(torch.optim.lr_scheduler, self.config.model.scheduler.name)
         scheduler = sched(optimizer, **filter_args(sched, self.config.model.scheduler))

@@ -1,8 +1,8 @@
-"""Flat parameter/gradient storage, bucketed gradient all-reduce (RCCL over xGMI) and the fused Adam optimizer.
+"""Flat parameter/gradient storage, bucketed gradient all-reduce (RCCL over xGMI) and the fused optimizers (Adam, AdamW, SGD).
 
 This is the MI355X-native replacement of the reference's dead Horovod path (``hvd.DistributedOptimizer`` in
 packnet_sfm/trainers/horovod_trainer.py:53-55: average every parameter gradient across ranks, overlapped with
-backward, waited in ``optimizer.step()``) and of ``torch.optim.Adam`` (models/model_wrapper.py:142-180).
+backward, waited in ``optimizer.step()``) and of ``torch.optim.Adam`` / ``AdamW`` / ``SGD`` (models/model_wrapper.py:142-180).
 
 One process per GPU.  Parameters live in ONE flat fp32 buffer (77 M elements = 308 MB) and gradients in another, laid
 out in *reverse execution order* so that gradient readiness during backward sweeps the buffer front to back.  The
@@ -11,7 +11,7 @@ asynchronous ``all_reduce`` per bucket on RCCL's stream the moment the bucket is
 decoder/late-encoder gradients overlaps the remaining backward.  xGMI is point-to-point (7 links/GPU): a few large
 messages amortise the ring's per-link latency better than 218 small ones, and the two huge tensors
 (pack5.conv 151 MB, pack4.conv 38 MB) finish early in backward, so their all-reduces hide under the high-resolution
-layers' backward.  ``step()`` waits for the outstanding collectives and runs one fused Adam kernel over the flat buffers.
+layers' backward.  ``step()`` waits for the outstanding collectives and runs one fused optimizer kernel over the flat buffers.
 """
 import os
 
@@ -191,18 +191,26 @@ class BucketedAllReduce:
                 "launch_offsets_mb": [round(s * 4 / 2**20, 2) for _, s, _, _ in getattr(self, "last_launches", [])]}
 
 
-class FusedAdam(torch.optim.Optimizer):
-    """torch.optim.Adam(lr, betas, eps, weight_decay=0) semantics as ONE HBM-bound kernel over the flat buffers
-    (28 B/parameter: read p,g,m,v; write p,m,v).  ``param_groups`` keeps torch's scheduler API (StepLR) working."""
+class FusedFlatOptimizer(torch.optim.Optimizer):
+    """What the fused optimizers share: ONE HBM-bound kernel over the flat buffers per step, with everything around it -- the reducer's
+    wait and its gradient scale, the gradient sink, the side stream, the weight-pack epoch and prefetch, the device error poll, the three
+    per-step scalars in device memory (``hyper``, refreshed by ``advance()`` through a pinned ring, so that the launch is the same every
+    step and replays from a HIP graph) and torch's own state-dict layout numbered in the reference's index space.  ``param_groups`` keeps
+    torch's scheduler API (StepLR) working.  A subclass names its group defaults (torch's key set for its class) and the group keys a
+    loaded file may set (LOAD_KEYS), and gives ``state_buffers`` ([(state-dict key, flat buffer)]), ``_hyper_values``, ``_launch``
+    (device scalars) and ``_host_step`` (host scalars)."""
 
-    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth'):
+    HAS_STEP = False                                         # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
+    LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
+    LOAD_KEYS = ('lr', 'initial_lr')
+
+    def __init__(self, flat, defaults, reducer=None, name='Depth'):
         self.flatp = flat
         self.reducer = reducer
-        super().__init__([{'params': flat.params, 'name': name}], dict(lr=lr, betas=betas, eps=eps))
-        self.exp_avg = torch.zeros_like(flat.flat)
-        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        super().__init__([{'params': flat.params, 'name': name}], defaults)
+        self._group_keys = tuple(defaults)
         self.steps = 0
-        self.hyper = torch.zeros(3, dtype=torch.float32, device=flat.flat.device)    # lr, 1 - b1^t, sqrt(1 - b2^t): read by the kernel
+        self.hyper = torch.zeros(3, dtype=torch.float32, device=flat.flat.device)    # read by the kernel (see _hyper_values)
         self._hyper_pinned = None
 
     def zero_grad(self, set_to_none=False):
@@ -222,28 +230,21 @@ class FusedAdam(torch.optim.Optimizer):
             # replay); under capture the host side of the step (advance) is the replaying caller's job
             if not torch.cuda.is_current_stream_capturing():
                 self.advance()
-            K.lib.mte_adam_step_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self.exp_avg.data_ptr(),
-                                    self.exp_avg_sq.data_ptr(), self.flatp.flat.numel(), self.hyper.data_ptr(),
-                                    float(g['betas'][0]), float(g['betas'][1]), float(g['eps']), float(gscale),
-                                    torch.cuda.current_stream().cuda_stream)
+            self._launch(K, g, float(gscale), torch.cuda.current_stream().cuda_stream)
             K.bump_weights_epoch()
         else:
             self.steps += 1
-            K.adam_step_flat(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.steps, lr=g['lr'],
-                             betas=g['betas'], eps=g['eps'], gscale=gscale)
+            self._host_step(K, g, gscale)                    # no CPU form: raises MteError on host buffers
         if self.flatp.grad.is_cuda:
             K.prefetch_weight_packs()                       # next step's kernel-ready weight packs, off the critical path
             if not torch.cuda.is_current_stream_capturing():
                 K.check_device_errors()                     # a bounded inter-workgroup wait gave up somewhere: fail the step (one host-memory read)
 
     def advance(self):
-        """Host side of one step: count it and hand the kernel its learning rate and bias corrections (same double-precision
-        arithmetic as mte_adam_step) -- called by step(), or by a graph-replaying caller right before each replay."""
-        import math
-        g = self.param_groups[0]
+        """Host side of one step: count it and hand the kernel its per-step scalars (same double-precision arithmetic as the
+        host-scalar entry point) -- called by step(), or by a graph-replaying caller right before each replay."""
         self.steps += 1
-        b1, b2 = g['betas']
-        vals = [float(g['lr']), 1.0 - math.pow(float(b1), self.steps), math.sqrt(1.0 - math.pow(float(b2), self.steps))]
+        vals = self._hyper_values(self.param_groups[0])
         if self.hyper.is_cuda and not os.environ.get("MTE_ADAM_PAGEABLE_HYPER"):
             # a copy from pageable memory makes the host wait for the stream (every step: the GPU then idles while the host catches
             # up with the next forward pass); a ring of pinned slots keeps the upload asynchronous.  Each slot carries the event of
@@ -265,7 +266,7 @@ class FusedAdam(torch.optim.Optimizer):
             self.hyper.copy_(torch.tensor(vals, dtype=torch.float32), non_blocking=True)
 
     def set_index_space(self, names, local_names):
-        """Number the optimizer state like the reference's ``torch.optim.Adam(depth_net.parameters())`` does.
+        """Number the optimizer state like the reference's ``torch.optim.<name>(depth_net.parameters())`` does.
 
         names: every parameter name of the reference network in ``depth_net.parameters()`` order -- frozen tensors and the
         sparse-branch (``mconvs.*``) tensors included, whether or not this build materialises them (reference
@@ -285,34 +286,45 @@ class FusedAdam(torch.optim.Optimizer):
         return out
 
     def state_dict(self):
-        """torch.optim.Adam's layout ({'state': {i: {'step','exp_avg','exp_avg_sq'}}, 'param_groups': [...]}).  Indices are
+        """The layout of the matching torch class ({'state': {i: {...}}, 'param_groups': [...]}: Adam / AdamW 'step', 'exp_avg',
+        'exp_avg_sq'; SGD 'momentum_buffer').  Indices are
         positions in the reference's ``depth_net.parameters()`` (see set_index_space): 'params' has one entry per reference
-        parameter, state entries exist for the tensors this build trains -- exactly what the reference's own Adam holds, since
+        parameter, state entries exist for the tensors this build trains -- exactly what the reference's own optimizer holds, since
         its sparse-branch tensors never receive a gradient on the RGB-only path and so never get state either
         (models/model_checkpoint.py:71-81 stores optimizer.state_dict())."""
         space = self._space()
         state = {}
-        if self.steps > 0:
+        bufs = self.state_buffers()
+        if self.steps > 0 and bufs:
             for i, (_, p, o) in enumerate(space):
                 if p is None:
                     continue
                 n = p.numel()
-                state[i] = {'step': torch.tensor(float(self.steps)), 'exp_avg': self.exp_avg[o:o + n].view(p.shape).clone(),
-                            'exp_avg_sq': self.exp_avg_sq[o:o + n].view(p.shape).clone()}
+                state[i] = {'step': torch.tensor(float(self.steps))} if self.HAS_STEP else {}
+                for key, b in bufs:
+                    state[i][key] = b[o:o + n].view(p.shape).clone()
         g = self.param_groups[0]
-        group = {'lr': g['lr'], 'betas': tuple(g['betas']), 'eps': g['eps'], 'weight_decay': 0.0, 'amsgrad': False,
-                 'maximize': False, 'foreach': None, 'capturable': False, 'differentiable': False, 'fused': None,
-                 'name': g.get('name', 'Depth'), 'params': list(range(len(space)))}
+        group = {k: (tuple(g[k]) if k == 'betas' else g[k]) for k in self._group_keys}
+        group.update({'name': g.get('name', 'Depth'), 'params': list(range(len(space)))})
         for k in ('initial_lr',):
             if k in g:
                 group[k] = g[k]
         return {'state': state, 'param_groups': [group]}
 
     def load_state_dict(self, sd):
-        if 'state' not in sd:                                   # flat layout written by earlier builds of this package
+        # the file's hyper-parameters win, as in torch (amsgrad / maximize are not built and stay off); first, since SGD's momentum
+        # decides whether a momentum buffer exists
+        for g, s_ in zip(self.param_groups, sd.get('param_groups', ())):
+            g.update({k: v for k, v in s_.items() if k in self.LOAD_KEYS})
+        bufs = self.state_buffers()
+        if 'state' not in sd:
+            # flat layout written by earlier builds of this package: they had Adam only (a file without 'param_groups' loads too)
+            if not self.LEGACY_FLAT:
+                raise ValueError("{} reads torch's optimizer layout only ({{'state', 'param_groups'}}); got keys {}".format(
+                    type(self).__name__, sorted(sd)))
             self.steps = sd['steps']
-            self.exp_avg.copy_(sd['exp_avg'])
-            self.exp_avg_sq.copy_(sd['exp_avg_sq'])
+            for key, b in bufs:
+                b.copy_(sd[key])
         else:
             space = self._space()
             groups = sd['param_groups']
@@ -324,23 +336,123 @@ class FusedAdam(torch.optim.Optimizer):
                     raise ValueError("optimizer state holds {} 'Depth' parameters; this network numbers {} ({} of them trained here)"
                                      .format(len(idx), len(space), len(trainable)))
                 space = trainable
-            self.exp_avg.zero_()
-            self.exp_avg_sq.zero_()
+            for _, b in bufs:
+                b.zero_()
             steps = 0
             for i, (name, p, o) in zip(idx, space):
                 st = sd['state'].get(i)
-                if st is None or p is None:                     # no state yet / a tensor this build does not hold (mconvs.*)
+                if st is None or p is None or not bufs:         # no state yet / a tensor this build does not hold (mconvs.*)
                     continue
-                if tuple(st['exp_avg'].shape) != tuple(p.shape):
-                    raise ValueError("optimizer state {} ({}) has shape {}, parameter has {}".format(
-                        i, name, tuple(st['exp_avg'].shape), tuple(p.shape)))
+                if any(st.get(key) is None for key, _ in bufs):
+                    continue                                    # torch's SGD writes momentum_buffer: None before a tensor's first gradient
                 n = p.numel()
-                self.exp_avg[o:o + n].copy_(st['exp_avg'].reshape(-1))
-                self.exp_avg_sq[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
-                steps = max(steps, int(float(st['step'])))
-            self.steps = steps                                  # torch keeps a step per tensor; they advance together here
-        for g, s_ in zip(self.param_groups, sd['param_groups']):
-            g.update({k: v for k, v in s_.items() if k in ('lr', 'betas', 'eps', 'initial_lr')})
+                for key, b in bufs:
+                    if tuple(st[key].shape) != tuple(p.shape):
+                        raise ValueError("optimizer state {} ({}) has shape {}, parameter has {}".format(
+                            i, name, tuple(st[key].shape), tuple(p.shape)))
+                    b[o:o + n].copy_(st[key].reshape(-1))
+                # torch keeps a step per tensor (Adam; they advance together here) or none (SGD: a buffer means "past the first step")
+                steps = max(steps, int(float(st['step'])) if self.HAS_STEP else 1)
+            self.steps = steps
+
+
+class FusedAdam(FusedFlatOptimizer):
+    """torch.optim.Adam(lr, betas, eps, weight_decay) -- or torch.optim.AdamW with ``decoupled_weight_decay=True`` -- as ONE HBM-bound
+    kernel over the flat buffers (28 B/parameter: read p,g,m,v; write p,m,v).  Without weight decay the launch is mte_adam_step_dev;
+    with it, mte_adamw_step_dev, which forms lr * weight_decay on the device from the step's own learning rate.
+
+    The step runs over EVERY element of the flat buffers.  torch skips a parameter whose ``.grad`` is None in a step: neither decay nor
+    moment update.  Here such a tensor has a zero gradient instead, so with a weight decay it still decays (and its moments decay
+    towards zero, as they always did) -- the SAN fusion scalars on the RGB-only path are the one case in this network."""
+
+    HAS_STEP = True
+    LEGACY_FLAT = True
+    LOAD_KEYS = ('lr', 'betas', 'eps', 'initial_lr', 'weight_decay', 'decoupled_weight_decay')
+
+    def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
+                 decoupled_weight_decay=False):
+        if not 0.0 <= float(weight_decay):
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
+                                    capturable=False, differentiable=False, fused=None,
+                                    decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name)
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+
+    def state_buffers(self):
+        return [('exp_avg', self.exp_avg), ('exp_avg_sq', self.exp_avg_sq)]
+
+    def _hyper_values(self, g):
+        """lr, 1 - b1^t, sqrt(1 - b2^t)"""
+        import math
+        b1, b2 = g['betas']
+        return [float(g['lr']), 1.0 - math.pow(float(b1), self.steps), math.sqrt(1.0 - math.pow(float(b2), self.steps))]
+
+    def _launch(self, K, g, gscale, stream):
+        wd = float(g['weight_decay'])
+        bufs = (self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.flatp.flat.numel(), self.hyper.data_ptr(), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']))
+        if wd == 0.0:
+            K.lib.mte_adam_step_dev(*bufs, gscale, stream)
+        else:
+            K.lib.mte_adamw_step_dev(*bufs, wd, int(bool(g['decoupled_weight_decay'])), gscale, stream)
+
+    def _host_step(self, K, g, gscale):
+        if float(g['weight_decay']) == 0.0:
+            K.adam_step_flat(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.steps, lr=g['lr'],
+                             betas=g['betas'], eps=g['eps'], gscale=gscale)
+        else:
+            K.adamw_step_flat(self.flatp.flat, self.flatp.grad, self.exp_avg, self.exp_avg_sq, self.steps, lr=g['lr'], betas=g['betas'],
+                              eps=g['eps'], weight_decay=g['weight_decay'], decoupled=g['decoupled_weight_decay'], gscale=gscale)
+
+
+class FusedSGD(FusedFlatOptimizer):
+    """torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) as ONE HBM-bound kernel over the flat buffers: 20 B/parameter
+    with momentum (read p,g,buf; write p,buf), 12 B without (no buffer exists then).  torch's first-step rule (buf = g') reaches the
+    kernel as the effective coefficients {lr, 0, 1} in ``hyper`` at step 1 and {lr, momentum, 1 - dampening} afterwards.
+
+    As with FusedAdam the step covers every element: a tensor without a gradient in a step (torch skips it) sees a zero gradient here, so
+    a weight decay still applies to it and its momentum buffer still decays."""
+
+    LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
+
+    def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth'):
+        if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
+            raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
+                                    maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name)
+        self.momentum_buffer = None
+        self.state_buffers()
+
+    def state_buffers(self):
+        """the momentum buffer, allocated (zero) when the group first asks for momentum -- at construction or when a loaded file does"""
+        if float(self.param_groups[0]['momentum']) == 0.0:
+            return []
+        if self.momentum_buffer is None:
+            self.momentum_buffer = torch.zeros_like(self.flatp.flat)
+        return [('momentum_buffer', self.momentum_buffer)]
+
+    def _hyper_values(self, g):
+        """lr, mu_eff, (1 - dampening)_eff"""
+        import struct
+        first = self.steps <= 1
+        damp = struct.unpack('f', struct.pack('f', float(g['dampening'])))[0]     # from the float32 dampening, as mte_sgd_step forms it
+        return [float(g['lr']), 0.0 if first else float(g['momentum']), 1.0 if first else 1.0 - damp]
+
+    def _buf_ptr(self):
+        bufs = self.state_buffers()
+        return bufs[0][1].data_ptr() if bufs else None
+
+    def _launch(self, K, g, gscale, stream):
+        K.lib.mte_sgd_step_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),
+                               self.hyper.data_ptr(), float(g['momentum']), float(g['weight_decay']), int(bool(g['nesterov'])), gscale, stream)
+
+    def _host_step(self, K, g, gscale):
+        bufs = self.state_buffers()
+        K.sgd_step_flat(self.flatp.flat, self.flatp.grad, bufs[0][1] if bufs else None, self.steps, lr=g['lr'], momentum=g['momentum'],
+                        dampening=g['dampening'], weight_decay=g['weight_decay'], nesterov=g['nesterov'], gscale=gscale)
 
 
 def reference_parameter_names(depth_net):

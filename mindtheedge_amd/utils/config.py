@@ -22,6 +22,9 @@ _DEFAULTS = {
     'arch': {'seed': 42, 'min_epochs': 1, 'max_epochs': 50, 'validate_first': False},
     'model': {
         'name': 'SemiSupEdgeModel', 'checkpoint_path': '',
+        # name: 'Adam', 'AdamW' or 'SGD' (default_config.py: model.optimizer.name).  depth: the keys torch.optim.<name> accepts reach the fused
+        # optimizer -- lr, weight_decay, betas, eps (Adam, AdamW); lr, weight_decay, momentum, dampening, nesterov (SGD); amsgrad / maximize: true
+        # are not built (ModelWrapper.configure_optimizers)
         'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}},
         'scheduler': {'name': 'StepLR', 'step_size': 10, 'gamma': 0.5},
         'params': {'crop': '', 'min_depth': 0.0, 'max_depth': 80.0, 'scale_output': 'resize'},     # default_config.py:84-87

@@ -108,7 +108,7 @@ class GraphedTrainStep:
         snap = {"torch_rng": torch.get_rng_state(), "cuda_rng": torch.cuda.get_rng_state(),
                 "buffers": [(b, b.detach().clone()) for b in self.model.buffers()]}
         if flat is not None:
-            snap.update(flat=flat.flat.clone(), m=opt.exp_avg.clone(), v=opt.exp_avg_sq.clone(), steps=opt.steps)
+            snap.update(flat=flat.flat.clone(), state=[(b, b.clone()) for _, b in opt.state_buffers()], steps=opt.steps)
         else:
             import copy
             snap.update(params=[(p, p.detach().clone()) for g in opt.param_groups for p in g["params"]],
@@ -122,8 +122,8 @@ class GraphedTrainStep:
         with torch.no_grad():
             if "flat" in snap:
                 opt.flatp.flat.copy_(snap["flat"])
-                opt.exp_avg.copy_(snap["m"])
-                opt.exp_avg_sq.copy_(snap["v"])
+                for b, v in snap["state"]:                  # Adam's moments / SGD's momentum buffer
+                    b.copy_(v)
                 opt.steps = snap["steps"]
             else:
                 for p, v in snap["params"]:
