@@ -235,6 +235,39 @@ int mte_copy_rect(const void* src, long lds_, int Hs, int Ws, int sy, int sx, vo
 typedef struct { const void* src; long lds_; int Hs, Ws, sy, sx; void* dst; long ldd; int Hd, Wd, dy, dx, h, w, mode; } mte_rect_op;
 int mte_copy_rects(const void* ops, int n, int B, int C, int dtype, mte_stream_t stream);
 
+/* ---- the exact border of a folded pack layer from a one-pixel ring (csrc/pack_border.hip, index arithmetic csrc/pack_border_plan.hpp).
+ *      The folded convolution runs over ALL pixels; within pad = k/2 pixels of the border it has seen conv3d's values outside the image, which the
+ *      reference (layers01.py:241-247, zero padding between conv3d and the k x k conv) does not.  They depend on the data only on the ring at
+ *      distance 1:  y_ref = y_fold - sum_{t: p+t on ring} W[t] . U(p+t) - sum_{t: p+t outside} S[t],  S[co][t] = sum_f b3[f] sum_d W[co][f*D+d][t].
+ *   P [B][H2][W2][D = 4C] is the packed tensor (pixel stride ldp).  Ring lines: R_rows [2B][W2+2][4D] = top then bottom row over x' = -1 .. W2,
+ *   R_cols [2B][H2][4D] = left then right column, contiguous, activation type; they hold U (conv3d's data part, no bias; fp32 sums rounded once).
+ *   The ring terms are two GEMMs per pass through mte_conv2d_igemm / mte_conv2d_wgrad: KH = 1, KW = k over R_rows and KH = k, KW = 1 over R_cols,
+ *   with N = 2 pad Co output columns (far edge, distance j, co) -> (far * pad + j) * Co + co and the NEGATED weights of mte_pack_border_weights
+ *   (row j of the near edge uses tap row pad-1-j, of the far edge pad+1+j; columns alike), results corr_rows [2B][W2+2][N] / corr_cols [2B][H2][N] in fp32 (out_f32 = 1).
+ *   mte_pack_border_apply adds them and the class table Dt [(2 pad + 1)^2][Co] to the border pixels of y in place, rounding once.
+ *   Backward: mte_pack_border_gather forms the GEMMs' gradient operand G_rows [2B][W2+2][N] / G_cols [2B][H2][N] from dy (zeros in the cross
+ *   blocks and at the rows' end positions); mte_pack_ring_bwd_data ACCUMULATES the ring stencil's transpose into the un-shuffled input gradient
+ *   dx [B][2 H2][2 W2][C] (its two outermost rows / columns); mte_pack_ring_bwd_weight adds the conv3d weight gradient to dk3 [108];
+ *   mte_pack_border_class_sums + mte_pack_border_scatter turn the ring-weight gradients and the class sums of dy into the dw_band argument of
+ *   mte_unfold_pack_wgrad (overwritten) and add the class path's db3 to dk3b [108 .. 112).  All sums have a fixed order: bit-reproducible.
+ *   Needs D % 32 == 0, Co % 8 == 0, k = 3 or 5, H2 and W2 >= 2 pad (smaller images and larger kernels: MTE_ERR_ARG; the host folds a layer only
+ *   where kernels.pack_fold_applicable allows it and runs the un-folded layer otherwise).  The *_elems queries size the fp32 work buffers (overwritten by the calls). */
+long mte_pack_ring_work_elems(void);
+long mte_pack_border_scatter_work_elems(int Co, int k);
+long mte_pack_border_class_sums_elems(int Co, int k);
+int mte_pack_ring_fwd(const void* P, long ldp, const float* K3, void* R_rows, void* R_cols, int B, int H2, int W2, int D, int dtype, mte_stream_t stream);
+int mte_pack_ring_bwd_data(const void* dR_rows, const void* dR_cols, const float* K3, void* dx, long lddx, int B, int H2, int W2, int D, int dtype,
+                           mte_stream_t stream);
+int mte_pack_ring_bwd_weight(const void* dR_rows, const void* dR_cols, const void* P, long ldp, float* dk3, float* work, int B, int H2, int W2, int D,
+                             int dtype, mte_stream_t stream);
+int mte_pack_border_weights(const float* W, const float* b3, float* Wr, float* Wc, float* Dt, int Co, int D, int k, mte_stream_t stream);
+int mte_pack_border_apply(void* y, long ldy, const float* corr_rows, const float* corr_cols, const float* Dt, int B, int H2, int W2, int Co, int k,
+                          int dtype, mte_stream_t stream);
+int mte_pack_border_gather(const void* dy, long lddy, void* G_rows, void* G_cols, int B, int H2, int W2, int Co, int k, int dtype, mte_stream_t stream);
+int mte_pack_border_class_sums(const void* dy, long lddy, float* part, int B, int H2, int W2, int Co, int k, int dtype, mte_stream_t stream);
+int mte_pack_border_scatter(const float* dWr, const float* dWc, const float* part, const float* W, const float* b3, float* dW, float* dk3b, float* work,
+                            int Co, int D, int k, mte_stream_t stream);
+
 /* ---- InvDepth head: sigmoid(conv3x3(x) + b) / min_depth  (layers01.py:99-123) */
 int mte_invdepth_fwd(const void* x, long ldx, const float* w, const float* bias, float* out,
                      int B, int H, int W, int C, float min_depth, int dtype, mte_stream_t stream);

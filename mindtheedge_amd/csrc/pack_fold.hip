@@ -10,10 +10,12 @@
 // which needs (k+2)^2 * 4C instead of k^2 * 16C multiply-adds per output (0.49x for the 5x5 pack1, 0.69x for the 3x3
 // packs) and never materialises the 16C-channel tensor T.  Within k/2 pixels of the border the two forms differ (the
 // reference zeroes T outside the image, the folded form sees conv3d's one-pixel spill-over and the bias only where T
-// exists); those thin bands are recomputed with the unfolded kernels by the host logic (kernels.PackFoldedConvFn).
+// exists); the difference depends on the data only on the one-pixel ring around the image and is added back exactly by
+// the kernels of pack_border.hip (host logic: kernels.PackFoldedConvGnEluFn), so the folded convolution and its
+// gradients run over all pixels.
 //
 // This file: the weight fold (forward), its transpose (backward: dW, dK3, db3 from dW', db'), pixel (un)shuffle between
-// x and P layouts, and a rectangle copy/add/zero used to cut and paste the border bands.
+// x and P layouts, and a rectangle copy/add/zero between NHWC tensors (a general helper; the folded layers no longer use it).
 #include "common.hpp"
 
 namespace {

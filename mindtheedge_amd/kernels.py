@@ -705,25 +705,6 @@ def use_wgrad_side_stream(flag):
     lib.set_option(3, 1 if flag else 0, lazy=True)           # MTE_OPT_WGRAD_SHARES_CHIP: the weight-gradient launch widths follow the schedule
 
 
-class _BandChain:
-    """The exact-border band chain of a folded pack layer (thin strips: 16 x 5 x 640 pixels and the like).  Rounds 3-5 could run it on a third stream beside the
-    layer's full-size kernels (MTE_BAND_STREAM=1: +0.4 % on one GPU, but 25.4 -> 35.1 ms per step as soon as RCCL's streams exist and the third stream shares a
-    hardware queue with one of the other two -- profiles/r03_band_stream_ab.txt); it lost that A/B and the option was removed in round 6.  What is left is the
-    bracket around the chain in PackFoldedConvGnEluFn: the chain runs on the current stream, `mark` / `join` are no-ops."""
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-    def mark(self):
-        return None
-
-    def join(self, ev=None):
-        return None
-
-
 def join_side_stream():
     """Make the current stream wait for every weight-gradient kernel queued on the side stream so far."""
     if _side["dirty"]:
@@ -1308,41 +1289,6 @@ class Unpack3dFn(torch.autograd.Function):
         return dx, dw3, db3, None
 
 
-def _rect(src, sy, sx, dst, dy, dx, h, w, mode=0):
-    """copy (0) / add (1) / zero (2) a [h x w] pixel rectangle between NHWC activations of equal batch and channels."""
-    B, C, Hd, Wd = dst.shape
-    dp, ldd = _pl(dst)
-    if mode == 2:
-        lib.mte_copy_rect(0, 0, 0, 0, 0, 0, dp, ldd, Hd, Wd, dy, dx, B, h, w, C, 2, _dt(dst), _stream())
-        return
-    sp, lds_ = _pl(src)
-    lib.mte_copy_rect(sp, lds_, src.shape[2], src.shape[3], sy, sx, dp, ldd, Hd, Wd, dy, dx, B, h, w, C, mode, _dt(dst), _stream())
-
-
-class _RectOp(ctypes.Structure):          # mte_rect_op of include/mte_kernels.h
-    _fields_ = [("src", ctypes.c_void_p), ("lds_", ctypes.c_long), ("Hs", ctypes.c_int), ("Ws", ctypes.c_int), ("sy", ctypes.c_int),
-                ("sx", ctypes.c_int), ("dst", ctypes.c_void_p), ("ldd", ctypes.c_long), ("Hd", ctypes.c_int), ("Wd", ctypes.c_int),
-                ("dy", ctypes.c_int), ("dx", ctypes.c_int), ("h", ctypes.c_int), ("w", ctypes.c_int), ("mode", ctypes.c_int)]
-
-
-def _rects(ops):
-    """Several _rect operations in one launch.  ops: (src or None, sy, sx, dst, dy, dx, h, w, mode) with equal batch/channels."""
-    arr = (_RectOp * len(ops))()
-    B = C = dt = None
-    for o, (src, sy, sx, dst, dy, dx, h, w, mode) in zip(arr, ops):
-        Bd, Cd, Hd, Wd = dst.shape
-        if B is None:
-            B, C, dt = Bd, Cd, _dt(dst)
-        elif (Bd, Cd, _dt(dst)) != (B, C, dt):
-            raise MteError("rectangle batch: mixed batch / channel / dtype")
-        dp, ldd = _pl(dst)
-        o.dst, o.ldd, o.Hd, o.Wd, o.dy, o.dx, o.h, o.w, o.mode = dp, ldd, Hd, Wd, dy, dx, h, w, mode
-        if mode != 2:
-            sp, lds_ = _pl(src)
-            o.src, o.lds_, o.Hs, o.Ws, o.sy, o.sx = sp, lds_, src.shape[2], src.shape[3], sy, sx
-    lib.mte_copy_rects(ctypes.addressof(arr), len(ops), B, C, dt, _stream())
-
-
 def _deliver(p, t):
     """hand a finished parameter gradient to the sink (flat buffer) or back to autograd"""
     sk = _sink["active"]
@@ -1423,8 +1369,10 @@ def _conv3d_weight_grads(kernel, x, dout, w3, b3):
 
 
 def pack_fold_applicable(H2, W2, k):
-    """Fold only when the exact-border bands are a small part of the image."""
+    """Fold only when the border (measured as the 2 * (k // 2) + 1 pixel bands the first form of the layer recomputed) is a small part of the image."""
     hb = 2 * (k // 2) + 1
+    if k > 5:                            # the border kernels (csrc/pack_border.hip) cover k = 3 and 5, the pack layers' sizes: larger filters stay un-folded
+        return False
     return H2 > 2 * hb and W2 > 2 * hb and (2.0 * hb / H2 + 2.0 * hb / W2) <= _cfg["pack_fold_max_overhead"]
 
 
@@ -1434,25 +1382,32 @@ def _fold_key(w, w3, b, b3):
 
 def _fold_now(f, w, w3, b, b3):
     co, C4, k = f["geom"]
-    lib.mte_fold_pack_weights(w.detach().data_ptr(), w3.detach().contiguous().float().data_ptr(), b.detach().data_ptr(),
-                              b3.detach().contiguous().float().data_ptr(), f["Wf"].data_ptr(), f["bf"].data_ptr(), co, C4, k, _stream())
+    w3c, b3c = w3.detach().contiguous().float(), b3.detach().contiguous().float()
+    lib.mte_fold_pack_weights(w.detach().data_ptr(), w3c.data_ptr(), b.detach().data_ptr(), b3c.data_ptr(), f["Wf"].data_ptr(), f["bf"].data_ptr(),
+                              co, C4, k, _stream())
+    # the border's ring weights (negated tap rows / columns of W, stacked per (edge, distance)) and class-bias table: csrc/pack_border.hip
+    lib.mte_pack_border_weights(w.detach().data_ptr(), b3c.data_ptr(), f["Wr"].data_ptr(), f["Wc"].data_ptr(), f["Dt"].data_ptr(), co, C4, k, _stream())
     f["key"] = _fold_key(w, w3, b, b3)
 
 
 def _folded_weights(pack_fold, w, w3, b, b3, co, C, k, dev):
-    """(W', b') of the folded pack convolution, kept per layer and re-folded only when a parameter changed: by the optimizer hook
+    """(W', b') of the folded pack convolution (and, in pack_fold.fold, the ring weights Wr / Wc with their packs and the class table Dt of the border), kept per layer and re-folded only when a parameter changed: by the optimizer hook
     below on the weight-pack side stream right after the update (70 us + two pack kernels per layer that used to sit on the main
     stream in front of the convolution), or here, inline, on first use / after an out-of-band parameter change."""
     f = getattr(pack_fold, "fold", None)
     if f is None or f["geom"] != (co, 4 * C, k) or f["Wf"].device != dev:
         f = pack_fold.fold = {"geom": (co, 4 * C, k), "key": None,
                               "Wf": torch.empty((co, 4 * C, k + 2, k + 2), dtype=torch.float32, device=dev),
-                              "bf": torch.empty((co,), dtype=torch.float32, device=dev)}
+                              "bf": torch.empty((co,), dtype=torch.float32, device=dev),
+                              "Wr": torch.empty((2 * (k // 2) * co, 16 * C, 1, k), dtype=torch.float32, device=dev),
+                              "Wc": torch.empty((2 * (k // 2) * co, 16 * C, k, 1), dtype=torch.float32, device=dev),
+                              "Dt": torch.empty((k * k, co), dtype=torch.float32, device=dev),
+                              "pk_r": WeightPack(), "pk_c": WeightPack()}
         _fold_hooks.append(weakref.ref(pack_fold))
     f["params"] = tuple(weakref.ref(t) for t in (w, w3, b, b3))
     if f["key"] != _fold_key(w, w3, b, b3) or _FOLD_INLINE:
         _fold_now(f, w, w3, b, b3)
-        pack_fold.key = None                               # the pack of W' is stale too
+        pack_fold.key = f["pk_r"].key = f["pk_c"].key = None          # the packs of W' and of the ring weights are stale too
     return f["Wf"], f["bf"]
 
 
@@ -1505,51 +1460,79 @@ def _dgrad_unshuffled(dy, Wf, pack, dx, k):
     return True
 
 
+def _ring_gemm(x, wpack, cout, kh, kw, out_f32, flags=0):
+    """one of a folded pack layer's border GEMMs: mte_conv2d_igemm with KH = 1 or KW = 1 along a ring line (x: a [2B, C, 1, n] or [2B, C, n, 1] activation).
+    -> fp32 [2B, n, cout] (out_f32: the forward ring terms, which mte_pack_border_apply adds to y un-rounded) or an activation of x's type (the data gradient).
+    flags: MTE_CONV_ACCUMULATE | MTE_CONV_SOLO"""
+    Bl, Cp, H, W = x.shape
+    xp, ldx = _pl(x)
+    if out_f32:
+        out = torch.empty((Bl, H * W, cout), dtype=torch.float32, device=x.device)
+        op, ldo = out.data_ptr(), cout
+    else:
+        out = new_act(Bl, cout, H, W, x.dtype, x.device)
+        op, ldo = _pl(out)
+    ws, ws_n = _splitk_workspace(Bl * H * W, cout, x.device)
+    lib.mte_conv2d_igemm(xp, ldx, wpack.data_ptr(), 0, op, ldo, 1 if out_f32 else 0, Bl, H, W, Cp, cout, kh, kw, _dt(x), _ptr(ws), ws_n, flags, _stream())
+    return out
+
+
+def _ring_wgrad(x, g, w):
+    """fp32 OIHW gradient of a ring weight tensor w [N, 16C, kh, kw] from the ring line x and the gathered gradient g.  Not _conv_wgrad: that one may route a
+    layer to the LDS-patch or nine-tap kernels, which are built and tested for square filters; a 1 x k / k x 1 filter takes the generic kernel (mte_conv2d_wgrad),
+    with at most 32 pixel splits so that mte_unpack_conv_wgrad adds the parts in one level (no scratch slabs)."""
+    cout, cin, kh, kw = w.shape
+    Bl, Cp, H, W = x.shape
+    xp, ldx = _pl(x)
+    gp, ldg = _pl(g)
+    per = cout * kh * kw * Cp
+    cap = max(1, min(32, (96 << 20) // (4 * per)))
+    stage = torch.empty((cap, cout, kh * kw, Cp), dtype=torch.float32, device=x.device)
+    parts = ctypes.c_int(1)
+    lib.mte_conv2d_wgrad(xp, ldx, gp, ldg, stage.data_ptr(), cap, ctypes.byref(parts), Bl, H, W, Cp, cout, kh, kw, _dt(x), _stream())
+    dw = torch.empty((cout, cin, kh, kw), dtype=torch.float32, device=x.device)
+    lib.mte_unpack_conv_wgrad(stage.data_ptr(), parts.value, dw.data_ptr(), cout, cin, kh, kw, Cp, _stream())
+    return dw
+
+
 class PackFoldedConvGnEluFn(torch.autograd.Function):
     """PackLayerConv3d as ONE (k+2)x(k+2) convolution over the packed tensor: conv3d(1->4) is folded into the k x k conv
-    weights (csrc/pack_fold.hip), halving the MACs of pack1 and removing the 16C-channel intermediate.  The k/2-pixel
-    border, where zero padding sits between the two reference ops (layers01.py:237-238 vs :31), is recomputed exactly
-    with the unfolded kernels on four thin bands and pasted over the folded result; backward mirrors it."""
+    weights (csrc/pack_fold.hip), halving the MACs of pack1 and removing the 16C-channel intermediate.  The folded convolution,
+    its data gradient and its weight gradient run over ALL pixels.  Within k/2 pixels of the border, where zero padding sits
+    between the two reference ops (layers01.py:237-238 vs :31), the folded form has seen conv3d's values outside the image; they
+    depend on the data only on the one-pixel ring around it, so the exact result is the folded one plus a 1 x k convolution along
+    the top / bottom ring rows, a k x 1 convolution along the left / right ring columns and a bias table over the pixel classes
+    (csrc/pack_border.hip).  Per pass: ring stencil + 2 GEMMs + apply (forward); gather + 2 GEMMs + ring data gradient (backward,
+    main queue); 2 weight-gradient GEMMs + scatter + ring weight gradient (backward, weight-gradient queue)."""
 
     @staticmethod
     def forward(ctx, x, w3, b3, w, b, gamma, beta, pack_unf, pack_fold, out=None):
         B, C, H, W = x.shape
         H2, W2 = H // 2, W // 2
         co, _, k, _ = w.shape
-        pad, hb = k // 2, 2 * (k // 2) + 1
+        pad, N = k // 2, 2 * (k // 2) * co
         dt, dev = _dt(x), x.device
         w3c, b3c = w3.detach().contiguous().float(), b3.detach().contiguous().float()
-        # exact border bands: group 1 = top/bottom rows, group 2 = left/right columns (rows pad .. H2-pad) -- a chain of small launches,
-        # on its own stream beside the interior path
-        bands = _BandChain()
-        with bands:
-            wu, _ = pack_unf.get(w, x.dtype, False)
-            xb1 = new_act(2 * B, C, 2 * hb, W, x.dtype, dev)
-            xb2 = new_act(2 * B, C, H, 2 * hb, x.dtype, dev)
-            _rects([(x, 0, 0, xb1[:B], 0, 0, 2 * hb, W, 0), (x, H - 2 * hb, 0, xb1[B:], 0, 0, 2 * hb, W, 0),
-                    (x, 0, 0, xb2[:B], 0, 0, H, 2 * hb, 0), (x, 0, W - 2 * hb, xb2[B:], 0, 0, H, 2 * hb, 0)])
-            Tb = []
-            for xb, (hh, ww) in ((xb1, (hb, W2)), (xb2, (H2, hb))):
-                T = new_act(2 * B, 16 * C, hh, ww, x.dtype, dev)
-                sp, lds_ = _pl(xb)
-                tp, ldt = _pl(T)
-                lib.mte_pack3d_fwd(sp, lds_, w3c.data_ptr(), b3c.data_ptr(), tp, ldt, 2 * B, xb.shape[2], xb.shape[3], C, dt, _stream())
-                Tb.append(T)
-            yb1 = conv_forward(Tb[0], wu, b, co, k, k, pack=pack_unf, w=w)
-            yb2 = conv_forward(Tb[1], wu, b, co, k, k, pack=pack_unf, w=w)
-        # folded weights + interior result
         P = new_act(B, 4 * C, H2, W2, x.dtype, dev)
         xp, ldx = _pl(x)
         pp, ldp = _pl(P)
         lib.mte_pixel_shuffle(xp, ldx, pp, ldp, B, H, W, C, 0, dt, _stream())
         Wf, bf = _folded_weights(pack_fold, w, w3, b, b3, co, C, k, dev)
+        f = pack_fold.fold
         wfp, _ = pack_fold.get(Wf, x.dtype, False)
         y = conv_forward(P, wfp, bf, co, k + 2, k + 2, pack=pack_fold, w=Wf)
-        bands.join()
-        _rects([(yb1[:B], 0, 0, y, 0, 0, pad, W2, 0), (yb1[B:], hb - pad, 0, y, H2 - pad, 0, pad, W2, 0),
-                (yb2[:B], pad, 0, y, pad, 0, H2 - 2 * pad, pad, 0), (yb2[B:], pad, hb - pad, y, pad, W2 - pad, H2 - 2 * pad, pad, 0)])
+        # the border: conv3d's data part on the ring, its two GEMMs with the (negated) ring weights, added to y with the class table
+        Rr = new_act(2 * B, 16 * C, 1, W2 + 2, x.dtype, dev)
+        Rc = new_act(2 * B, 16 * C, H2, 1, x.dtype, dev)
+        lib.mte_pack_ring_fwd(pp, ldp, w3c.data_ptr(), Rr.data_ptr(), Rc.data_ptr(), B, H2, W2, 4 * C, dt, _stream())
+        wr, _ = f["pk_r"].get(f["Wr"], x.dtype, False)
+        wc, _ = f["pk_c"].get(f["Wc"], x.dtype, False)
+        cr = _ring_gemm(Rr, wr, N, 1, k, True, _CONV_SOLO)
+        cc = _ring_gemm(Rc, wc, N, k, 1, True, _CONV_SOLO)
+        yp, ldy = _pl(y)
+        lib.mte_pack_border_apply(yp, ldy, cr.data_ptr(), cc.data_ptr(), f["Dt"].data_ptr(), B, H2, W2, co, k, dt, _stream())
         z, stats = _gn_forward(y, None, None, gamma, beta, GN_EPS, out=None if out is None else alias_of(out))
-        ctx.save_for_backward(P, xb1, xb2, Tb[0], Tb[1], y, stats, w, w3c, b3c, gamma, beta, Wf)
+        ctx.save_for_backward(P, Rr, Rc, y, stats, w, w3c, b3c, gamma, beta, Wf)
         ctx.params = (w3, b3, b)
         ctx.packs = (pack_unf, pack_fold)
         ctx.geom = (B, C, H, W, co, k)
@@ -1557,85 +1540,67 @@ class PackFoldedConvGnEluFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, dz):
-        P, xb1, xb2, T1, T2, y, stats, w, w3c, b3c, gamma, beta, Wf = ctx.saved_tensors
+        P, Rr, Rc, y, stats, w, w3c, b3c, gamma, beta, Wf = ctx.saved_tensors
         w3, b3, b = ctx.params
         pack_unf, pack_fold = ctx.packs
         B, C, H, W, co, k = ctx.geom
-        H2, W2, pad, hb = H // 2, W // 2, k // 2, 2 * (k // 2) + 1
+        H2, W2, pad, N = H // 2, W // 2, k // 2, 2 * (k // 2) * co
         dt, dev = _dt(P), P.device
+        f = pack_fold.fold
         gg, sg = _grad_dst(gamma, zero=True)
         gbt, sbt = _grad_dst(beta, zero=True)
         dy, _, dgamma, dbeta = _gn_backward(dz, y, None, None, stats, gamma, beta, GN_EPS, False, dgamma=gg, dbeta=gbt)
-        # ---- band paths (unfolded, exact), beside the interior path
-        bands = _BandChain()
-        with bands:
-            dyb1 = torch.zeros((2 * B, hb, W2, co), dtype=P.dtype, device=dev).permute(0, 3, 1, 2)
-            dyb2 = torch.zeros((2 * B, H2, hb, co), dtype=P.dtype, device=dev).permute(0, 3, 1, 2)
-            _rects([(dy, 0, 0, dyb1[:B], 0, 0, pad, W2, 0), (dy, H2 - pad, 0, dyb1[B:], hb - pad, 0, pad, W2, 0),
-                    (dy, pad, 0, dyb2[:B], pad, 0, H2 - 2 * pad, pad, 0), (dy, pad, W2 - pad, dyb2[B:], pad, hb - pad, H2 - 2 * pad, pad, 0)])
-            gathered = bands.mark()                            # the band pixels of dy have been read (they are cleared below)
-            dTs, dxb = [], []
-            for xb, T, dyb in ((xb1, T1, dyb1), (xb2, T2, dyb2)):
-                dT, _, _ = conv_backward(T, dyb, w, pack_unf, True, need_dw=False)
-                Bb, _, hx, wx = xb.shape
-                tp, ldt = _pl(dT)
-                dxi = new_act(Bb, C, hx, wx, P.dtype, dev)
-                dp_, ldd = _pl(dxi)
-                lib.mte_pack3d_bwd_data(tp, ldt, w3c.data_ptr(), dp_, ldd, Bb, hx, wx, C, dt, _stream())
-                dTs.append(dT)
-                dxb.append(dxi)
-        # ---- interior path (folded): band pixels carry no gradient here
-        bands.join(gathered)
-        _rects([(None, 0, 0, dy, 0, 0, pad, W2, 2), (None, 0, 0, dy, H2 - pad, 0, pad, W2, 2),
-                (None, 0, 0, dy, pad, 0, H2 - 2 * pad, pad, 2), (None, 0, 0, dy, pad, W2 - pad, H2 - 2 * pad, pad, 2)])
+        dyp, lddy = _pl(dy)
+        pp, ldp = _pl(P)
+        # ---- border, main queue: dy of the border pixels as the ring GEMMs' gradient operand, then the gradient of the ring lines
+        Gr = new_act(2 * B, N, 1, W2 + 2, P.dtype, dev)
+        Gc = new_act(2 * B, N, H2, 1, P.dtype, dev)
+        lib.mte_pack_border_gather(dyp, lddy, Gr.data_ptr(), Gc.data_ptr(), B, H2, W2, co, k, dt, _stream())
+        _, wrb = f["pk_r"].get(f["Wr"], P.dtype, True)
+        _, wcb = f["pk_c"].get(f["Wc"], P.dtype, True)
+        dRr = _ring_gemm(Gr, wrb, 16 * C, 1, k, False)
+        dRc = _ring_gemm(Gc, wcb, 16 * C, k, 1, False)
 
         def weight_grads():
             """every parameter gradient of the layer except gamma/beta; nothing on the data-gradient chain needs them"""
-            bands.join()                                       # (on the stream that runs the weight gradients: they read dTs / dyb)
             sw = _stream()
-            dw_band = db_band = None
-            # (round 4) the parameter gradients are formed IN their places in the flat gradient buffer where the sink hands them out (zero after zero_grad):
-            # the four `_deliver` copies of this layer were eight ~4 us blit kernels
+            # (round 4) the parameter gradients are formed IN their places in the flat gradient buffer where the sink hands them out (zero after zero_grad)
             dst3 = _claim_adjacent(w3, b3)
             dk3b = dst3 if dst3 is not None else torch.zeros((112,), dtype=torch.float32, device=dev)
             gw_dst, gw_sunk = _grad_dst(w)
             gb_dst, gb_sunk = _grad_dst(b)
-            for xb, T, dyb, dT in ((xb1, T1, dyb1, dTs[0]), (xb2, T2, dyb2, dTs[1])):
-                dwi, dbi = _conv_wgrad(T, dyb, w, True, gw_dst if dw_band is None else None, None)
-                dw_band = dwi if dw_band is None else dw_band.add_(dwi)
-                db_band = dbi if db_band is None else db_band.add_(dbi)
-                Bb, _, hx, wx = xb.shape
-                tmp = torch.empty((112,), dtype=torch.float32, device=dev)
-                sp, lds_ = _pl(xb)
-                tp, ldt = _pl(dT)
-                lib.mte_pack3d_bwd_weight(sp, lds_, tp, ldt, tmp.data_ptr(), Bb, hx, wx, C, dt, sw)
-                dk3b.add_(tmp)
-            dWf, dbf = _conv_wgrad(P, dy, Wf, True, None, None)
-            lib.mte_unfold_pack_wgrad(dWf.data_ptr(), dbf.data_ptr(), w.detach().data_ptr(), w3c.data_ptr(), b3c.data_ptr(),
-                                      dw_band.data_ptr(), dk3b.data_ptr(), co, 4 * C, k, 1, sw)
-            db = torch.add(dbf, db_band, out=gb_dst)
+            part = torch.empty((int(lib.mte_pack_border_class_sums_elems(co, k)),), dtype=torch.float32, device=dev)
+            lib.mte_pack_border_class_sums(dyp, lddy, part.data_ptr(), B, H2, W2, co, k, dt, sw)
+            dWr = _ring_wgrad(Rr, Gr, f["Wr"])
+            dWc = _ring_wgrad(Rc, Gc, f["Wc"])
+            work = torch.empty((int(lib.mte_pack_border_scatter_work_elems(co, k)) + int(lib.mte_pack_ring_work_elems()),), dtype=torch.float32, device=dev)
+            lib.mte_pack_border_scatter(dWr.data_ptr(), dWc.data_ptr(), part.data_ptr(), w.detach().data_ptr(), b3c.data_ptr(), gw_dst.data_ptr(),
+                                        dk3b.data_ptr(), work.data_ptr(), co, 4 * C, k, sw)
+            lib.mte_pack_ring_bwd_weight(dRr.data_ptr(), dRc.data_ptr(), pp, ldp, dk3b.data_ptr(),
+                                         work.data_ptr() + 4 * int(lib.mte_pack_border_scatter_work_elems(co, k)), B, H2, W2, 4 * C, dt, sw)
+            dWf, db = _conv_wgrad(P, dy, Wf, True, None, gb_dst)       # (the folded bias gradient is the layer's: the class table carries b3 only)
+            lib.mte_unfold_pack_wgrad(dWf.data_ptr(), db.data_ptr(), w.detach().data_ptr(), w3c.data_ptr(), b3c.data_ptr(),
+                                      gw_dst.data_ptr(), dk3b.data_ptr(), co, 4 * C, k, 1, sw)
             if dst3 is not None:
                 _announce(w3, b3)
                 g3 = gb3 = None
             else:
                 g3, gb3 = _deliver_pair(w3, b3, dk3b, 108)
-            return (g3, gb3, _grad_ret(w, dw_band, gw_sunk), _grad_ret(b, db, gb_sunk))
+            return (g3, gb3, _grad_ret(w, gw_dst, gw_sunk), _grad_ret(b, db, gb_sunk))
 
         if _side["enabled"] and _all_sunk(w3, b3, w, b):
-            with torch.cuda.stream(_side_stream_for(P, dy, T1, T2, dyb1, dyb2, dTs[0], dTs[1], xb1, xb2, Wf)):
+            with torch.cuda.stream(_side_stream_for(P, dy, Rr, Rc, Gr, Gc, dRr, dRc, Wf)):
                 g3, gb3, gw, gb = weight_grads()
         else:
             g3, gb3, gw, gb = weight_grads()
         dx = new_act(B, C, H, W, P.dtype, dev)
+        dxp, lddx = _pl(dx)
         if not _dgrad_unshuffled(dy, Wf, pack_fold, dx, k + 2):
             dP, _, _ = conv_backward(P, dy, Wf, pack_fold, True, need_dw=False)
             sp, lds_ = _pl(dP)
-            dp_, ldd = _pl(dx)
-            lib.mte_pixel_shuffle(sp, lds_, dp_, ldd, B, H, W, C, 1, dt, _stream())
-        bands.join()
-        # (the four bands overlap in the corners: two launches so that no element is read-modified by two operations at once)
-        _rects([(dxb[0][:B], 0, 0, dx, 0, 0, 2 * hb, W, 1), (dxb[0][B:], 0, 0, dx, H - 2 * hb, 0, 2 * hb, W, 1)])
-        _rects([(dxb[1][:B], 0, 0, dx, 0, 0, H, 2 * hb, 1), (dxb[1][B:], 0, 0, dx, 0, W - 2 * hb, H, 2 * hb, 1)])
+            lib.mte_pixel_shuffle(sp, lds_, dxp, lddx, B, H, W, C, 1, dt, _stream())
+        # the ring stencil's transpose, accumulated into the two outermost rows / columns of dx
+        lib.mte_pack_ring_bwd_data(dRr.data_ptr(), dRc.data_ptr(), w3c.data_ptr(), dxp, lddx, B, H2, W2, 4 * C, dt, _stream())
         return (dx, g3, gb3, gw, gb, _grad_ret(gamma, dgamma, sg), _grad_ret(beta, dbeta, sbt), None, None, None)
 
 
