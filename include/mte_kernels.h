@@ -433,6 +433,25 @@ int mte_sgd_step(float* p, const float* g, float* buf, long n, float lr, float m
                  int step, float gscale, mte_stream_t stream);
 int mte_sgd_step_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
                      float gscale, mte_stream_t stream);
+/* ---- gradient-norm clipping and the non-finite step guard (csrc/optim.hip): torch.nn.utils.clip_grad_norm_ (L2) over the flat gradient
+ * without a pass that rescales it, and a step that is dropped on the device when a gradient is not finite.
+ * mte_grad_norm_clip: ONE read-only launch over g[0..n) (16-byte aligned), fp64 sums in a fixed order (bit-equal run to run and under
+ *   graph replay; no floating-point atomics).  With S = sum g^2 and norm = |gscale| * sqrt(S) it writes ctl (four floats, DEVICE memory):
+ *     ctl[0] = max_norm / (norm + 1e-6), replaced by 1 where that is > 1 (max_norm = +inf gives exactly 1; a NaN stays a NaN)
+ *     ctl[1] = 1 if skip_nonfinite and S is not finite, else 0
+ *     ctl[2] = norm
+ *     ctl[3] += 1 when ctl[1] is set: a running count of skipped steps that the kernel never resets
+ *   `work`: mte_grad_norm_work_bytes(n) bytes, 16-byte aligned, zeroed ONCE by the caller; its first 8 bytes receive S (fp64).
+ *   max_norm <= 0 or NaN, n <= 0 and null pointers are MTE_ERR_ARG.
+ * mte_adamw_step_ctl_dev / mte_sgd_step_ctl_dev: mte_adamw_step_dev / mte_sgd_step_dev whose gradient scale is float32(gscale * ctl[0])
+ *   and which, with ctl[1] != 0, return before their first load: p, m, v / buf keep their bits.  ctl = {1, 0} is the plain step bit for
+ *   bit.  The host cannot know that a step was skipped: its step count (the bias corrections in `hyper`) advances all the same. */
+long mte_grad_norm_work_bytes(long n);
+int mte_grad_norm_clip(const float* g, long n, float gscale, float max_norm, int skip_nonfinite, void* work, float* ctl, mte_stream_t stream);
+int mte_adamw_step_ctl_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                           float weight_decay, int decoupled, float gscale, const float* ctl, mte_stream_t stream);
+int mte_sgd_step_ctl_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
+                         float gscale, const float* ctl, mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

@@ -402,3 +402,17 @@ def sgd_step_flat(p, g, buf, step, lr=1e-3, momentum=0.0, dampening=0.0, weight_
     _K.lib.mte_sgd_step(p.data_ptr(), g.data_ptr(), None if buf is None else buf.data_ptr(), p.numel(), float(lr), float(momentum),
                         float(dampening), float(weight_decay), int(bool(nesterov)), int(step), float(gscale), _K._stream())
     _K.bump_weights_epoch()
+
+
+def grad_norm_work(n, device):
+    """the zeroed work buffer of grad_norm_clip_flat for n gradient elements (records and ticket; allocate once, reuse every step)"""
+    return torch.zeros((int(_K.lib.mte_grad_norm_work_bytes(int(n))) + 7) // 8, dtype=torch.float64, device=device)
+
+
+def grad_norm_clip_flat(g, work, ctl, gscale=1.0, max_norm=float('inf'), skip_nonfinite=False, stream=None):
+    """Global L2 norm of the flat fp32 gradient ``g`` in one read-only launch with a fixed summation order; leaves ``ctl`` (four floats on
+    the device) = {min(max_norm / (|gscale| * norm + 1e-6), 1), skip flag, |gscale| * norm, skipped steps} for the ``_ctl_dev`` optimizer
+    steps and the fp64 sum of squares in ``work[0]``.  No host synchronisation."""
+    _K._require_gpu(g)
+    _K.lib.mte_grad_norm_clip(g.data_ptr(), g.numel(), float(gscale), float(max_norm), int(bool(skip_nonfinite)), work.data_ptr(), ctl.data_ptr(),
+                              _K._stream() if stream is None else stream)

@@ -198,13 +198,28 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     step and replays from a HIP graph) and torch's own state-dict layout numbered in the reference's index space.  ``param_groups`` keeps
     torch's scheduler API (StepLR) working.  A subclass names its group defaults (torch's key set for its class) and the group keys a
     loaded file may set (LOAD_KEYS), and gives ``state_buffers`` ([(state-dict key, flat buffer)]), ``_hyper_values``, ``_launch``
-    (device scalars) and ``_host_step`` (host scalars)."""
+    (device scalars), ``_launch_ctl`` (the same with ``ctl``) and ``_host_step`` (host scalars).
+
+    Gradient-norm clipping and the non-finite step guard (``clip_grad_norm`` > 0: torch.nn.utils.clip_grad_norm_'s L2 rule with that
+    max_norm; ``skip_nonfinite``: a step whose gradient holds an inf or a NaN changes nothing).  With both off -- the default -- the step
+    is the one described above: no buffer, no launch, no entry point is added.  With either on, ``step()`` launches mte_grad_norm_clip
+    over the flat gradient (one read-only pass, fp64 sums in a fixed order) and then the ``_ctl_dev`` form of the step, which reads
+    ``ctl`` = {clip coefficient, skip flag, gradient norm, skipped steps} from device memory: the gradient buffer is never rescaled, both
+    launches are identical every step (HIP-graph replay), and the host learns nothing -- ``grad_stats()`` is the one host read, for
+    tests and logging.  Across ranks the norm is taken after the all-reduce has finished, over the summed buffer with gscale = 1/world;
+    all-reduce leaves the same bits on every rank, so every rank forms the same ``ctl`` and skips the same steps.
+    Deviation from a host-side guard: the host cannot know that a step was skipped, so ``steps`` advances anyway -- Adam's bias
+    correction counts skipped steps, and SGD's first-step rule belongs to step 1 whether or not it was skipped.  Neither setting is
+    part of ``state_dict()``: they come from the configuration, not from the file."""
 
     HAS_STEP = False                                         # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
     LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
     LOAD_KEYS = ('lr', 'initial_lr')
 
-    def __init__(self, flat, defaults, reducer=None, name='Depth'):
+    def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False):
+        if not float(clip_grad_norm) >= 0.0:
+            raise ValueError("Invalid clip_grad_norm value: {} (0 = off)".format(clip_grad_norm))
+        self.clip_grad_norm, self.skip_nonfinite = float(clip_grad_norm), bool(skip_nonfinite)
         self.flatp = flat
         self.reducer = reducer
         super().__init__([{'params': flat.params, 'name': name}], defaults)
@@ -212,6 +227,24 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         self.steps = 0
         self.hyper = torch.zeros(3, dtype=torch.float32, device=flat.flat.device)    # read by the kernel (see _hyper_values)
         self._hyper_pinned = None
+        if self.clip_grad_norm > 0.0 or self.skip_nonfinite:
+            # only then: the default optimizer has no `ctl` attribute, no work buffer and no norm launch
+            self.ctl = torch.zeros(4, dtype=torch.float32, device=flat.flat.device)
+            self._norm_work = None                            # the norm launch's records and ticket: zeroed ONCE, here
+            if flat.flat.is_cuda:
+                from .. import kernels as K
+                self._norm_work = K.grad_norm_work(flat.grad.numel(), flat.flat.device)
+
+    def grad_stats(self):
+        """{'grad_norm', 'clip_coef', 'skipped', 'skipped_steps'} of the last step as Python numbers: ONE host read (it waits for the
+        device), for tests and logging"""
+        c = self.ctl.tolist()
+        return {'grad_norm': c[2], 'clip_coef': c[0], 'skipped': bool(c[1]), 'skipped_steps': int(c[3])}
+
+    def _norm_clip(self, K, gscale, stream):
+        """ctl <- the clip coefficient / skip flag of the gradient as it stands (reduced and complete)"""
+        K.grad_norm_clip_flat(self.flatp.grad, self._norm_work, self.ctl, gscale, self.clip_grad_norm if self.clip_grad_norm > 0.0 else float('inf'),
+                              self.skip_nonfinite, stream)
 
     def zero_grad(self, set_to_none=False):
         self.flatp.zero_grad()
@@ -230,7 +263,12 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             # replay); under capture the host side of the step (advance) is the replaying caller's job
             if not torch.cuda.is_current_stream_capturing():
                 self.advance()
-            self._launch(K, g, float(gscale), torch.cuda.current_stream().cuda_stream)
+            stream = torch.cuda.current_stream().cuda_stream
+            if getattr(self, 'ctl', None) is None:
+                self._launch(K, g, float(gscale), stream)
+            else:
+                self._norm_clip(K, float(gscale), stream)
+                self._launch_ctl(K, g, float(gscale), stream)
             K.bump_weights_epoch()
         else:
             self.steps += 1
@@ -370,12 +408,13 @@ class FusedAdam(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'betas', 'eps', 'initial_lr', 'weight_decay', 'decoupled_weight_decay')
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
-                 decoupled_weight_decay=False):
+                 decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False):
         if not 0.0 <= float(weight_decay):
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
         super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                     capturable=False, differentiable=False, fused=None,
-                                    decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name)
+                                    decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name,
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
 
@@ -388,10 +427,18 @@ class FusedAdam(FusedFlatOptimizer):
         b1, b2 = g['betas']
         return [float(g['lr']), 1.0 - math.pow(float(b1), self.steps), math.sqrt(1.0 - math.pow(float(b2), self.steps))]
 
+    def _bufs(self, g):
+        return (self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
+                self.flatp.flat.numel(), self.hyper.data_ptr(), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']))
+
+    def _launch_ctl(self, K, g, gscale, stream):
+        """clipped / guarded: weight_decay = 0 is adamw_kernel's WD_NONE instance, the Adam step operation for operation"""
+        K.lib.mte_adamw_step_ctl_dev(*self._bufs(g), float(g['weight_decay']), int(bool(g['decoupled_weight_decay'])), gscale,
+                                     self.ctl.data_ptr(), stream)
+
     def _launch(self, K, g, gscale, stream):
         wd = float(g['weight_decay'])
-        bufs = (self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(),
-                self.flatp.flat.numel(), self.hyper.data_ptr(), float(g['betas'][0]), float(g['betas'][1]), float(g['eps']))
+        bufs = self._bufs(g)
         if wd == 0.0:
             K.lib.mte_adam_step_dev(*bufs, gscale, stream)
         else:
@@ -416,13 +463,15 @@ class FusedSGD(FusedFlatOptimizer):
 
     LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
 
-    def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth'):
+    def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth',
+                 clip_grad_norm=0.0, skip_nonfinite=False):
         if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
             raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
-                                    maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name)
+                                    maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name,
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
         self.momentum_buffer = None
         self.state_buffers()
 
@@ -448,6 +497,11 @@ class FusedSGD(FusedFlatOptimizer):
     def _launch(self, K, g, gscale, stream):
         K.lib.mte_sgd_step_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),
                                self.hyper.data_ptr(), float(g['momentum']), float(g['weight_decay']), int(bool(g['nesterov'])), gscale, stream)
+
+    def _launch_ctl(self, K, g, gscale, stream):
+        K.lib.mte_sgd_step_ctl_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),
+                                   self.hyper.data_ptr(), float(g['momentum']), float(g['weight_decay']), int(bool(g['nesterov'])), gscale,
+                                   self.ctl.data_ptr(), stream)
 
     def _host_step(self, K, g, gscale):
         bufs = self.state_buffers()

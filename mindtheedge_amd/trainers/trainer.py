@@ -93,6 +93,15 @@ class Trainer:
         module.train()
         run = torch.zeros(3, device=self.device)               # loss, supervised, edge running sums (device side)
         n, last = 0, None
+        # a clipping / guarding optimizer leaves ctl = {clip coefficient, skip flag, gradient norm, skipped steps} on the device: the norm
+        # joins the running sums (a skipped step's norm is inf or NaN and counts as 0), the count is read with them
+        ctl = getattr(optimizer, 'ctl', None)
+        gsum = torch.zeros((), device=self.device) if ctl is not None else None
+
+        def read():
+            """the running means as Python numbers (+ mean gradient norm and skipped steps with a ctl): one host read"""
+            return (run / n).tolist() if ctl is None else torch.cat([run / n, (gsum / n).reshape(1), ctl[3:4]]).tolist()
+
         for i, batch in enumerate(dataloader):
             optimizer.zero_grad()
             batch = sample_to_cuda(batch, self.device)
@@ -102,11 +111,19 @@ class Trainer:
             m = output['metrics']
             zero = run.new_zeros(())
             run += torch.stack([output['loss'].detach().sum(), m.get('supervised_loss', zero).sum(), m.get('edge_loss', zero).sum()])
+            if ctl is not None:
+                gsum += torch.where(torch.isfinite(ctl[2]), ctl[2], torch.zeros_like(ctl[2]))
             n += 1
             if self.is_rank_0 and self.log_every and n % self.log_every == 0:
-                last = (run / n).tolist()                       # the only host sync
-                print('step {} | Avg. {:.4f} | Sup. {:.4f} | Edge RGB {:.4f}'.format(n, *last), flush=True)
+                last = read()                                   # the only host sync
+                line = 'step {} | Avg. {:.4f} | Sup. {:.4f} | Edge RGB {:.4f}'.format(n, *last[:3])
+                if ctl is not None:
+                    line += ' | Grad norm {:.4f} | Skipped {}'.format(last[3], int(last[4]))
+                print(line, flush=True)
         if n:
-            last = (run / n).tolist()
-        return {'steps': n, 'avg_loss': last[0] if last else None, 'avg_supervised': last[1] if last else None,
-                'avg_edge': last[2] if last else None}
+            last = read()
+        out = {'steps': n, 'avg_loss': last[0] if last else None, 'avg_supervised': last[1] if last else None,
+               'avg_edge': last[2] if last else None}
+        if ctl is not None:
+            out.update(avg_grad_norm=last[3] if last else None, skipped_steps=int(last[4]) if last else 0)
+        return out

@@ -24,8 +24,10 @@ _DEFAULTS = {
         'name': 'SemiSupEdgeModel', 'checkpoint_path': '',
         # name: 'Adam', 'AdamW' or 'SGD' (default_config.py: model.optimizer.name).  depth: the keys torch.optim.<name> accepts reach the fused
         # optimizer -- lr, weight_decay, betas, eps (Adam, AdamW); lr, weight_decay, momentum, dampening, nesterov (SGD); amsgrad / maximize: true
-        # are not built (ModelWrapper.configure_optimizers)
-        'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}},
+        # are not built (ModelWrapper.configure_optimizers).  clip_grad_norm (0 = off): torch.nn.utils.clip_grad_norm_'s max_norm over all trained
+        # tensors; skip_nonfinite_steps: a step whose gradient holds an inf or a NaN changes nothing.  Both are this package's own keys and sit
+        # beside `name`, not under `depth`, so filter_args never hands them to torch.optim; both off = the step as it always was.
+        'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}, 'clip_grad_norm': 0.0, 'skip_nonfinite_steps': False},
         'scheduler': {'name': 'StepLR', 'step_size': 10, 'gamma': 0.5},
         'params': {'crop': '', 'min_depth': 0.0, 'max_depth': 80.0, 'scale_output': 'resize'},     # default_config.py:84-87
         'loss': {'supervised_method': 'sparse-l1', 'supervised_num_scales': 4, 'supervised_loss_weight': 0.9,
