@@ -452,6 +452,11 @@ int mte_adamw_step_ctl_dev(float* p, const float* g, float* m, float* v, long n,
                            float weight_decay, int decoupled, float gscale, const float* ctl, mte_stream_t stream);
 int mte_sgd_step_ctl_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
                          float gscale, const float* ctl, mte_stream_t stream);
+/* ---- gradient accumulation over micro-batches (csrc/optim.hip): one streaming launch in the step kernels' shape, no atomics, no state.
+ * assign = 0: dst[i] = dst[i] + src[i] in fp32, one rounding (12 B per element: read, read, write); assign != 0: dst[i] = src[i], a bit
+ *   copy that does not read dst.  n = 0 returns 0 without a launch.  n < 0, a null pointer, a pointer that is not 16-byte aligned and
+ *   overlapping ranges (equal pointers included) are MTE_ERR_ARG. */
+int mte_grad_accumulate(float* dst, const float* src, long n, int assign, mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

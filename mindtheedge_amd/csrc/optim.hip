@@ -16,8 +16,12 @@
 // ctl = {clip coefficient, skip flag, norm, skipped steps} in device memory, and the device-scalar steps' CTL form (mte_adamw_step_ctl_dev,
 // mte_sgd_step_ctl_dev) multiplies gscale by ctl[0] or, with ctl[1] set, returns before its first load.  Without CTL the kernels are the
 // instruction streams they were (profiles/grad_clip.txt).
+//
+// Gradient accumulation: mte_grad_accumulate adds (or copies) one flat buffer into another in the same launch shape -- the micro-batch
+// sum of FusedFlatOptimizer(accumulate_grad_batches > 1).  It is a kernel of its own: nothing is added to the step kernels.
 #include "common.hpp"
 #include "handoff.hpp"
+#include <cstdint>
 #include <type_traits>
 
 namespace {
@@ -235,9 +239,46 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_norm_kernel(NormArgs a) {
     if (skip) a.ctl[3] = a.ctl[3] + 1.f;
 }
 
+// ---- gradient accumulation over micro-batches --------------------------------------------------------------------------------------------
+// dst[i] = dst[i] + src[i] (one fp32 rounding), or with ASSIGN dst[i] = src[i] (a bit copy: dst is not read), in the step kernels' launch
+// shape.  12 B per element without ASSIGN (read, read, write): the plain SGD launch's count and read:write mix.  No atomics, no state.
+template <bool ASSIGN>
+__global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float* __restrict__ dst, const float* __restrict__ src, long n) {
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4_t s = ((const f32x4_t*)src)[i];
+        if (!ASSIGN) {
+            const f32x4_t d = ((const f32x4_t*)dst)[i];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) s[k] = d[k] + s[k];
+        }
+        ((f32x4_t*)dst)[i] = s;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        dst[i] = ASSIGN ? src[i] : dst[i] + src[i];
+    }
+}
+
 }  // namespace
 
 extern "C" {
+
+// Gradient accumulation over flat fp32 buffers (16-byte aligned, disjoint): assign = 0 adds src into dst, dst[i] = dst[i] + src[i] with one
+// fp32 rounding; assign = 1 copies src's bits.  n = 0 launches nothing.  n < 0, a null or misaligned pointer and overlapping ranges
+// (equal pointers included) are MTE_ERR_ARG.
+int mte_grad_accumulate(float* dst, const float* src, long n, int assign, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    const uintptr_t d = (uintptr_t)dst, s = (uintptr_t)src;
+    if (!dst || !src || n < 0 || ((d | s) & 15) || d == s) return MTE_ERR_ARG;
+    if (n == 0) return 0;
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+    if (d < s + bytes && s < d + bytes) return MTE_ERR_ARG;
+    const dim3 grid(opt_grid(n >> 2)), block(OPT_THREADS);
+    if (assign) hipLaunchKernelGGL(grad_accumulate_kernel<true>, grid, block, 0, stream, dst, src, n);
+    else hipLaunchKernelGGL(grad_accumulate_kernel<false>, grid, block, 0, stream, dst, src, n);
+    return mte_check_launch();
+}
 
 // Bytes of `work` for mte_grad_norm_clip over n elements (16-byte aligned, zeroed ONCE by the caller): {S, ticket, pad, one record per workgroup}.
 long mte_grad_norm_work_bytes(long n) { return n <= 0 ? 0 : NORM_HEAD_BYTES + 8L * norm_grid(n >> 2); }

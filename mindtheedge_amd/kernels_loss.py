@@ -404,6 +404,16 @@ def sgd_step_flat(p, g, buf, step, lr=1e-3, momentum=0.0, dampening=0.0, weight_
     _K.bump_weights_epoch()
 
 
+def grad_accumulate_flat(dst, src, assign=False, stream=None):
+    """dst <- dst + src in fp32 with one rounding per element, or with ``assign`` dst <- src (a bit copy), over two disjoint flat fp32
+    device buffers of one size: ONE streaming launch (the micro-batch sum of gradient accumulation)."""
+    _K._require_gpu(dst)
+    _K._require_gpu(src)
+    if dst.dtype != torch.float32 or src.dtype != torch.float32 or dst.numel() != src.numel() or not (dst.is_contiguous() and src.is_contiguous()):
+        raise MteError("grad_accumulate_flat takes two contiguous float32 buffers of one size")
+    _K.lib.mte_grad_accumulate(dst.data_ptr(), src.data_ptr(), dst.numel(), int(bool(assign)), _K._stream() if stream is None else stream)
+
+
 def grad_norm_work(n, device):
     """the zeroed work buffer of grad_norm_clip_flat for n gradient elements (records and ticket; allocate once, reuse every step)"""
     return torch.zeros((int(_K.lib.mte_grad_norm_work_bytes(int(n))) + 7) // 8, dtype=torch.float64, device=device)

@@ -96,7 +96,8 @@ class ModelWrapper(nn.Module):
         lr, weight_decay, betas, eps, momentum, dampening and nesterov work when a YAML names them.  The optimizer is the fused flat
         one of that name and carries the bucketed RCCL gradient averaging when torch.distributed is initialised.
         config.model.optimizer.clip_grad_norm / skip_nonfinite_steps (this package's keys, beside `name`) switch on the device-side
-        gradient-norm clipping and non-finite step guard of FusedFlatOptimizer."""
+        gradient-norm clipping and non-finite step guard of FusedFlatOptimizer; config.arch.accumulate_grad_batches > 1 its gradient
+        accumulation over micro-batches."""
         import torch.distributed as dist
         from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedSGD, broadcast_parameters,
                                               reference_parameter_names)
@@ -121,8 +122,13 @@ class ModelWrapper(nn.Module):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
             broadcast_parameters(flat, group=process_group)
             reducer = BucketedAllReduce(flat, process_group)
+        # arch.accumulate_grad_batches micro-batches per optimizer step; a trainer that was given its own value hands it over (Trainer.fit
+        # attaches itself before it asks for the optimizer)
+        accumulate = getattr(self.trainer, 'accumulate_grad_batches', None)
+        if accumulate is None:
+            accumulate = self.config.arch.accumulate_grad_batches or 1
         optimizer = built[opt_cfg.name](flat, reducer=reducer, name='Depth', clip_grad_norm=float(opt_cfg.clip_grad_norm or 0.0),
-                                        skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), **kwargs)
+                                        skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), accumulate_grad_batches=accumulate, **kwargs)
         optimizer.set_index_space(reference_parameter_names(self.depth_net), dict(self.depth_net.named_parameters()))
         sched = getattr(torch.optim.lr_scheduler, self.config.model.scheduler.name)
         scheduler = sched(optimizer, **filter_args(sched, self.config.model.scheduler))

@@ -13,6 +13,7 @@ messages amortise the ring's per-link latency better than 218 small ones, and th
 (pack5.conv 151 MB, pack4.conv 38 MB) finish early in backward, so their all-reduces hide under the high-resolution
 layers' backward.  ``step()`` waits for the outstanding collectives and runs one fused optimizer kernel over the flat buffers.
 """
+import contextlib
 import os
 
 import torch
@@ -45,6 +46,7 @@ class FlatParameters:
             view.copy_(p.data)
             p.data = view
             p.grad = self.grad[o:o + p.numel()].view(p.shape)
+        self.accum = None                                    # the micro-batch sum of gradient accumulation: see enable_accumulation
         self.sink = None
         if dev.type == "cuda":
             # backward kernels store conv / GroupNorm parameter gradients straight into self.grad (no per-tensor add)
@@ -53,6 +55,13 @@ class FlatParameters:
             for p in order:
                 self.sink.register(p, p.grad)
             K.set_grad_sink(self.sink)
+
+    def enable_accumulation(self):
+        """``accum``: a second flat fp32 buffer of ``total`` elements (+4 B per parameter) that holds the sum of a group's earlier
+        micro-batch gradients.  It exists only for an optimizer built with accumulate_grad_batches > 1."""
+        if self.accum is None:
+            self.accum = torch.zeros_like(self.grad)
+        return self.accum
 
     def zero_grad(self):
         if self.grad.is_cuda:
@@ -106,6 +115,8 @@ class BucketedAllReduce:
         self._works = []
         self._hooks = []
         self._stream = None         # collectives are issued from here (see _launch)
+        self.sync = True            # False inside no_sync(): gradients of a micro-batch that is not the last of its group stay local
+        self._fold = None           # FlatParameters.accum while earlier micro-batches of the group wait in it (set by accumulate())
         self.active = self.world > 1 or (force and dist.is_available() and dist.is_initialized())   # force: single-rank RCCL tests
         if self.active:
             for p in flat.params:
@@ -114,6 +125,8 @@ class BucketedAllReduce:
                 flat.sink.on_ready = self._on_grad_ready      # gradients written in place never reach AccumulateGrad
 
     def _on_grad_ready(self, p):
+        if not self.sync:
+            return
         if id(p) in self._seen:
             return
         self._seen.add(id(p))
@@ -132,10 +145,17 @@ class BucketedAllReduce:
             s += n
         return out
 
+    def fold_pending(self, accum):
+        """From now until finish(): every bucket first takes ``accum``'s elements of its range, grad[s:e] += accum[s:e], and is reduced
+        after that -- the earlier micro-batches of an accumulation group join the last one's gradient bucket by bucket, each once."""
+        self._fold = accum
+
     def _launch(self, s, e, b=-1):
         msgs = self._messages(s, e)
         self.launch_log.append((b, s, e - s, len(msgs)))
         if not self.flat.grad.is_cuda:
+            if self._fold is not None:
+                self.flat.grad[s:e].add_(self._fold[s:e])
             for ms, me in msgs:
                 self._works.append(dist.all_reduce(self.flat.grad[ms:me], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
             return
@@ -148,6 +168,9 @@ class BucketedAllReduce:
         self._stream.wait_stream(torch.cuda.current_stream())
         K.side_streams_wait_into(self._stream)
         with torch.cuda.stream(self._stream):
+            if self._fold is not None:
+                # on the reduction stream, behind its waits for the main stream (accumulate()'s launches) and the side stream
+                K.grad_accumulate_flat(self.flat.grad[s:e], self._fold[s:e], assign=False)
             for ms, me in msgs:
                 self._works.append(dist.all_reduce(self.flat.grad[ms:me], op=dist.ReduceOp.SUM, group=self.group, async_op=True))
 
@@ -173,6 +196,7 @@ class BucketedAllReduce:
         self.last_launches = self.launch_log
         self._works, self._ready, self.launch_log = [], [0] * len(self.buckets), []
         self._seen.clear()
+        self._fold = None
         return 1.0 / self.world
 
     def exposed_ms(self):
@@ -210,15 +234,36 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     all-reduce leaves the same bits on every rank, so every rank forms the same ``ctl`` and skips the same steps.
     Deviation from a host-side guard: the host cannot know that a step was skipped, so ``steps`` advances anyway -- Adam's bias
     correction counts skipped steps, and SGD's first-step rule belongs to step 1 whether or not it was skipped.  Neither setting is
-    part of ``state_dict()``: they come from the configuration, not from the file."""
+    part of ``state_dict()``: they come from the configuration, not from the file.
+
+    Gradient accumulation (``accumulate_grad_batches`` = k > 1): up to k micro-batches share one optimizer step, so that one card runs
+    the global batch a recipe was tuned for.  Every micro-batch is the zero_grad -> forward -> backward it always was; for all but the
+    last of a group the caller runs forward and backward inside ``no_sync()`` (the reducer drops the ready announcements: no collective)
+    and calls ``accumulate()`` in place of ``step()``: ONE mte_grad_accumulate launch adds the flat gradient into a second flat buffer,
+    ``FlatParameters.accum`` (+4 B per parameter; the first of a group assigns, so the buffer is never cleared).  ``step()`` with j >= 1
+    micro-batches pending folds ``accum`` back into the gradient before anything reads it -- bucket by bucket on the reduction stream
+    in front of each bucket's all-reduce when a reducer is active (the all-reduce still overlaps the last micro-batch's backward), else
+    in one launch over the whole buffer -- and scales by 1 / (world * (j + 1)).  Summation order: the gradient the step consumes is
+    the fp32 sum (((g0 + g1) + ...) + g_j) per element, g_i the i-th micro-batch's gradient, each addition rounded once; it is what
+    ``flat.grad`` holds after the step.  The norm launch and the ``_ctl_dev`` step see that sum with that scale: the clip applies to the
+    averaged gradient, and an inf or NaN in any micro-batch skips the step.  A group may be shorter than k (an epoch's end).  ``steps``
+    advances once per step().  With k = 1 -- the default -- there is no buffer and no launch, and ``step()`` with nothing pending is the
+    step described above bit for bit.  Neither the setting nor ``accum`` is part of ``state_dict()``: checkpoints are written where
+    no group is open."""
 
     HAS_STEP = False                                         # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
     LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
     LOAD_KEYS = ('lr', 'initial_lr')
 
-    def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False):
+    def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
         if not float(clip_grad_norm) >= 0.0:
             raise ValueError("Invalid clip_grad_norm value: {} (0 = off)".format(clip_grad_norm))
+        if int(accumulate_grad_batches) != accumulate_grad_batches or int(accumulate_grad_batches) < 1:
+            raise ValueError("Invalid accumulate_grad_batches value: {} (an integer >= 1; 1 = off)".format(accumulate_grad_batches))
+        self.accumulate_grad_batches = int(accumulate_grad_batches)
+        self._pending = 0                                     # micro-batches of the open group that wait in flat.accum
+        if self.accumulate_grad_batches > 1:
+            flat.enable_accumulation()                        # only then: the default optimizer has no second gradient buffer
         self.clip_grad_norm, self.skip_nonfinite = float(clip_grad_norm), bool(skip_nonfinite)
         self.flatp = flat
         self.reducer = reducer
@@ -249,12 +294,61 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     def zero_grad(self, set_to_none=False):
         self.flatp.zero_grad()
 
+    @contextlib.contextmanager
+    def no_sync(self):
+        """``with optimizer.no_sync():`` around the forward and backward of a micro-batch that is not the last of its accumulation
+        group: the reducer drops the ready announcements, so it counts nothing and launches no collective (without a reducer the
+        block changes nothing)"""
+        red = self.reducer
+        prev = red is not None and red.sync
+        if red is not None:
+            red.sync = False
+        try:
+            yield
+        finally:
+            if red is not None:
+                red.sync = prev
+
+    @torch.no_grad()
+    def accumulate(self):
+        """In place of step() for a micro-batch that is not the last of its group: accum <- grad (the group's first) or accum + grad,
+        one launch on the current stream.  No step is counted, no weight moves, the weights epoch and the device error word are left
+        alone."""
+        from .. import kernels as K
+        k, flat, red = self.accumulate_grad_batches, self.flatp, self.reducer
+        if k == 1:
+            raise RuntimeError("accumulate() needs an optimizer built with accumulate_grad_batches > 1")
+        if self._pending >= k - 1:
+            raise RuntimeError("{} micro-batches are already accumulated: the {}-th of a group of accumulate_grad_batches = {} "
+                               "ends in step()".format(self._pending, k, k))
+        if red is not None and (red.launch_log or red._works):
+            raise RuntimeError("the gradient all-reduce launched a collective during this micro-batch's backward: run the forward and "
+                               "backward of a micro-batch that ends in accumulate() inside optimizer.no_sync()")
+        if flat.grad.is_cuda:
+            K.join_side_stream()                              # weight gradients arrive on the side queue
+        if flat.sink is not None:
+            flat.sink.end_step()
+        if flat.grad.is_cuda:
+            K.grad_accumulate_flat(flat.accum, flat.grad, assign=self._pending == 0)
+        elif self._pending == 0:                              # host buffers (the gloo CPU tests), as BucketedAllReduce._launch
+            flat.accum.copy_(flat.grad)
+        else:
+            flat.accum.add_(flat.grad)
+        self._pending += 1
+        if red is not None and red.active:
+            red.fold_pending(flat.accum)                      # the next backward's buckets take accum before they are reduced
+
     @torch.no_grad()
     def step(self, closure=None):
         from .. import kernels as K
         if self.flatp.grad.is_cuda:
             K.join_side_stream()
         gscale = self.reducer.finish() if self.reducer is not None else 1.0
+        if self._pending:
+            if self.reducer is None or not self.reducer.active:
+                K.grad_accumulate_flat(self.flatp.grad, self.flatp.accum, assign=False)      # (an active reducer folded bucket by bucket)
+            gscale = 1.0 / ((self.reducer.world if self.reducer is not None else 1) * (self._pending + 1))
+            self._pending = 0
         if self.flatp.sink is not None:
             self.flatp.sink.end_step()                       # (a forward pass's gradient-sink suspension lasts until its gradients are consumed)
         g = self.param_groups[0]
@@ -408,13 +502,13 @@ class FusedAdam(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'betas', 'eps', 'initial_lr', 'weight_decay', 'decoupled_weight_decay')
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
-                 decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False):
+                 decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
         if not 0.0 <= float(weight_decay):
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
         super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                     capturable=False, differentiable=False, fused=None,
                                     decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name,
-                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
 
@@ -464,14 +558,14 @@ class FusedSGD(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
 
     def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth',
-                 clip_grad_norm=0.0, skip_nonfinite=False):
+                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
         if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
             raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                     maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name,
-                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches)
         self.momentum_buffer = None
         self.state_buffers()
 

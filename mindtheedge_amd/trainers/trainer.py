@@ -19,10 +19,49 @@ def sample_to_cuda(data, device):
     return data
 
 
+def accumulation_groups(n_batches, k):
+    """Sizes of the accumulation groups that n_batches micro-batches form at k per optimizer step, in order: full groups of k and,
+    where k does not divide n_batches, one trailing short group (which steps too).  (5, 2) -> [2, 2, 1]; k = 1 -> all ones."""
+    if int(k) < 1 or int(n_batches) < 0:
+        raise ValueError("accumulation_groups({}, {}): n_batches >= 0 and k >= 1".format(n_batches, k))
+    full, rest = divmod(int(n_batches), int(k))
+    return [int(k)] * full + ([rest] if rest else [])
+
+
+def _with_group_end(dataloader, k):
+    """(batch, True for the last micro-batch of its accumulation group) for every batch of the loader.  With a length the groups are
+    accumulation_groups(len, k); a loader without one is read one batch ahead, which finds the same ends."""
+    if k == 1:
+        for batch in dataloader:
+            yield batch, True
+    elif hasattr(dataloader, '__len__'):
+        ends, at = set(), 0
+        for size in accumulation_groups(len(dataloader), k):
+            at += size
+            ends.add(at)
+        for i, batch in enumerate(dataloader):
+            yield batch, (i + 1) in ends
+    else:
+        it, end, in_group = iter(dataloader), object(), 0
+        ahead = next(it, end)
+        while ahead is not end:
+            batch, ahead = ahead, next(it, end)
+            in_group += 1
+            last = in_group == k or ahead is end
+            if last:
+                in_group = 0
+            yield batch, last
+
+
 class Trainer:
-    def __init__(self, min_epochs=0, max_epochs=50, validate_first=False, checkpoint=None, log_every=50, **kwargs):
+    def __init__(self, min_epochs=0, max_epochs=50, validate_first=False, checkpoint=None, log_every=50, accumulate_grad_batches=None,
+                 **kwargs):
         self.min_epochs, self.max_epochs, self.validate_first = min_epochs, max_epochs, validate_first
         self.checkpoint, self.log_every = checkpoint, log_every
+        # micro-batches per optimizer step (arch.accumulate_grad_batches); None: what the module's configuration says
+        if accumulate_grad_batches is not None and int(accumulate_grad_batches) < 1:
+            raise ValueError("Invalid accumulate_grad_batches value: {} (an integer >= 1; 1 = off)".format(accumulate_grad_batches))
+        self.accumulate_grad_batches = None if accumulate_grad_batches is None else int(accumulate_grad_batches)
         self.distributed = int(os.environ.get('WORLD_SIZE', '1')) > 1
         if self.distributed and not dist.is_initialized():
             local = int(os.environ.get('LOCAL_RANK', '0'))
@@ -50,6 +89,9 @@ class Trainer:
         module.trainer = self
         module.to(self.device)
         optimizer, scheduler = module.configure_optimizers()
+        if self.accumulate_grad_batches not in (None, getattr(optimizer, 'accumulate_grad_batches', 1)):
+            raise ValueError("Trainer(accumulate_grad_batches={}) but the module's optimizer was built with {}".format(
+                self.accumulate_grad_batches, getattr(optimizer, 'accumulate_grad_batches', 1)))
         if train_dataloader is None:
             train_dataloader = module.train_dataloader()
         if val_dataloaders is None:
@@ -93,6 +135,10 @@ class Trainer:
         module.train()
         run = torch.zeros(3, device=self.device)               # loss, supervised, edge running sums (device side)
         n, last = 0, None
+        # gradient accumulation: k micro-batches per optimizer step (1: every batch steps, the loop below is the plain one).  The loss sums
+        # stay per batch; the gradient norm is one per optimizer step and is averaged over those
+        k = getattr(optimizer, 'accumulate_grad_batches', 1)
+        nsteps = 0
         # a clipping / guarding optimizer leaves ctl = {clip coefficient, skip flag, gradient norm, skipped steps} on the device: the norm
         # joins the running sums (a skipped step's norm is inf or NaN and counts as 0), the count is read with them
         ctl = getattr(optimizer, 'ctl', None)
@@ -100,18 +146,25 @@ class Trainer:
 
         def read():
             """the running means as Python numbers (+ mean gradient norm and skipped steps with a ctl): one host read"""
-            return (run / n).tolist() if ctl is None else torch.cat([run / n, (gsum / n).reshape(1), ctl[3:4]]).tolist()
+            return (run / n).tolist() if ctl is None else torch.cat([run / n, (gsum / max(nsteps, 1)).reshape(1), ctl[3:4]]).tolist()
 
-        for i, batch in enumerate(dataloader):
+        for i, (batch, steps) in enumerate(_with_group_end(dataloader, k)):
             optimizer.zero_grad()
             batch = sample_to_cuda(batch, self.device)
-            output = module.training_step(batch, i, None)
-            output['loss'].backward()
-            optimizer.step()
+            if steps:
+                output = module.training_step(batch, i, None)
+                output['loss'].backward()
+                optimizer.step()
+                nsteps += 1
+            else:                                               # not the last of its group: no collective, the gradient joins the group's sum
+                with optimizer.no_sync():
+                    output = module.training_step(batch, i, None)
+                    output['loss'].backward()
+                optimizer.accumulate()
             m = output['metrics']
             zero = run.new_zeros(())
             run += torch.stack([output['loss'].detach().sum(), m.get('supervised_loss', zero).sum(), m.get('edge_loss', zero).sum()])
-            if ctl is not None:
+            if ctl is not None and steps:
                 gsum += torch.where(torch.isfinite(ctl[2]), ctl[2], torch.zeros_like(ctl[2]))
             n += 1
             if self.is_rank_0 and self.log_every and n % self.log_every == 0:
@@ -126,4 +179,6 @@ class Trainer:
                'avg_edge': last[2] if last else None}
         if ctl is not None:
             out.update(avg_grad_norm=last[3] if last else None, skipped_steps=int(last[4]) if last else 0)
+        if k > 1:
+            out['optimizer_steps'] = nsteps
         return out

@@ -19,7 +19,9 @@ class Cfg(dict):
 
 _DEFAULTS = {
     'is_multi_gpu': False,
-    'arch': {'seed': 42, 'min_epochs': 1, 'max_epochs': 50, 'validate_first': False},
+    # accumulate_grad_batches (this package's key): micro-batches per optimizer step.  The reference reaches its global batch through Horovod
+    # (8 per GPU x N GPUs); k > 1 runs that effective batch on fewer cards (FusedFlatOptimizer.accumulate).  1 = every batch steps.
+    'arch': {'seed': 42, 'min_epochs': 1, 'max_epochs': 50, 'validate_first': False, 'accumulate_grad_batches': 1},
     'model': {
         'name': 'SemiSupEdgeModel', 'checkpoint_path': '',
         # name: 'Adam', 'AdamW' or 'SGD' (default_config.py: model.optimizer.name).  depth: the keys torch.optim.<name> accepts reach the fused

@@ -64,6 +64,9 @@ class GraphedTrainStep:
         self.model, self.opt = model, optimizer
         self.batch = {k: (v.clone() if torch.is_tensor(v) else v) for k, v in example_batch.items()}
         self.graphs, self.outs, self.error = {}, {}, None
+        if getattr(optimizer, "accumulate_grad_batches", 1) > 1:
+            raise NotImplementedError("GraphedTrainStep captures one batch per optimizer step: an optimizer built with "
+                                      "accumulate_grad_batches > 1 runs its groups on the eager path (Trainer.train)")
         if getattr(optimizer, "reducer", None) is not None and getattr(optimizer.reducer, "active", False):
             self.error = "gradient all-reduce active: eager step"
             return
