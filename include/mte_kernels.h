@@ -267,6 +267,20 @@ int mte_pack_border_gather(const void* dy, long lddy, void* G_rows, void* G_cols
 int mte_pack_border_class_sums(const void* dy, long lddy, float* part, int B, int H2, int W2, int Co, int k, int dtype, mte_stream_t stream);
 int mte_pack_border_scatter(const float* dWr, const float* dWc, const float* part, const float* W, const float* b3, float* dW, float* dk3b, float* work,
                             int Co, int D, int k, mte_stream_t stream);
+/* The forward ring terms in ONE grouped split-K launch (csrc/pack_border_gemm.hip, launch plan plan_pack_border_gemm in csrc/pack_border_plan.hpp), bf16:
+ *   line-batch (far', b) only uses the columns (far, j, co) with far == far', so the two GEMMs are four of half the width (ring rows / columns x near / far
+ *   edge); one grid covers their 128 x 64 tiles times `splits` slices of K = k * C16 (C16 = 4D = 16C channels of a ring line), chosen so that the launch
+ *   fills the chip.  Slice s leaves its partial tile in slab s of its family: ws = fp32 [splits][2B][W2+2][N] then [splits][2B][H2][N], each slab in the
+ *   layout of corr_rows / corr_cols (columns with far != far' are not written).  mte_pack_border_apply_slabs = mte_pack_border_apply reading that
+ *   workspace: every term is the sum of its slabs in slab order, formed where it is added to y.  No atomics, fixed order: bit-reproducible.
+ *   mte_pack_border_gemm_ws_elems returns the workspace's fp32 elements and stores the slice count in *splits, or MTE_ERR_UNSUPPORTED (as the launch does)
+ *   for fp32 and for shapes outside C16 % 32 == 0, Co % 8 == 0, k = 3 or 5: the caller then takes the two mte_conv2d_igemm launches + mte_pack_border_apply.
+ *   Wr_pack / Wc_pack: the forward packs [N][k][C16] of mte_pack_border_weights' Wr / Wc (mte_pack_conv_weights).  force_splits: 0; tests pass a slice count. */
+long mte_pack_border_gemm_ws_elems(int B, int H2, int W2, int C16, int Co, int k, int dtype, int force_splits, int* splits);
+int mte_pack_border_gemm_fwd(const void* R_rows, const void* R_cols, const void* Wr_pack, const void* Wc_pack, float* ws, long ws_elems, int B, int H2, int W2,
+                             int C16, int Co, int k, int dtype, int force_splits, mte_stream_t stream);
+int mte_pack_border_apply_slabs(void* y, long ldy, const float* ws, int splits, const float* Dt, int B, int H2, int W2, int Co, int k, int dtype,
+                                mte_stream_t stream);
 
 /* ---- InvDepth head: sigmoid(conv3x3(x) + b) / min_depth  (layers01.py:99-123) */
 int mte_invdepth_fwd(const void* x, long ldx, const float* w, const float* bias, float* out,

@@ -12,7 +12,7 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libmte_hip.so")
-SOURCES = ["conv_igemm.hip", "conv_igemm8.hip", "conv_wgrad9.hip", "tap_wgrad.hip", "conv_patch.hip", "conv_stem.hip", "norm_act.hip", "pack3d.hip", "pack_fold.hip", "pack_border.hip", "heads_misc.hip", "optim.hip", "edge_loss.hip", "edge_loss_kinds.hip", "supervised_loss.hip", "eval_metrics.hip", "dee_post.hip", "chamfer.hip", "canny.hip", "edge_match.hip", "san.hip", "data_prep.hip", "batch_prep.hip", "eval_prep.hip", "image_prep.hip", "lidar_prep.hip", "depth_viz.hip"]
+SOURCES = ["conv_igemm.hip", "conv_igemm8.hip", "conv_wgrad9.hip", "tap_wgrad.hip", "conv_patch.hip", "conv_stem.hip", "norm_act.hip", "pack3d.hip", "pack_fold.hip", "pack_border.hip", "pack_border_gemm.hip", "heads_misc.hip", "optim.hip", "edge_loss.hip", "edge_loss_kinds.hip", "supervised_loss.hip", "eval_metrics.hip", "dee_post.hip", "chamfer.hip", "canny.hip", "edge_match.hip", "san.hip", "data_prep.hip", "batch_prep.hip", "eval_prep.hip", "image_prep.hip", "lidar_prep.hip", "depth_viz.hip"]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-value", "-ffp-contract=off"]
 
 

@@ -261,10 +261,13 @@ __global__ __launch_bounds__(256) void border_weights_kernel(const float* __rest
     }
 }
 
-// y [B][H2][W2][Co] += corr_rows [2B][W2+2][N] / corr_cols [2B][H2][N] (fp32, N = 2 pad Co) + Dt[class] on the border pixels; fp32 sum, rounded once
+// y [B][H2][W2][Co] += corr_rows [2B][W2+2][N] / corr_cols [2B][H2][N] (fp32, N = 2 pad Co) + Dt[class] on the border pixels; fp32 sum, rounded once.
+// splits > 1: the ring terms arrive as `splits` slabs of partial sums (mte_pack_border_gemm_fwd), slab_r / slab_c elements apart; each term is the sum of its
+// slabs in slab order, formed here -- no finish launch, the summed terms are never written
 template <typename T>
 __global__ __launch_bounds__(256) void border_apply_kernel(T* __restrict__ y, long ldy, const float* __restrict__ cr, const float* __restrict__ cc,
-                                                           const float* __restrict__ Dt, int B, int H2, int W2, int Co, int pad) {
+                                                           const float* __restrict__ Dt, int B, int H2, int W2, int Co, int pad,
+                                                           int splits, long slab_r, long slab_c) {
     constexpr int P = Elem<T>::PER16;
     const int cpr = Co / P, N = 2 * pad * Co, nc = 2 * pad + 1;
     const long npix = pb_border_count(H2, W2, pad), total = (long)B * npix * cpr;
@@ -288,7 +291,9 @@ __global__ __launch_bounds__(256) void border_apply_kernel(T* __restrict__ y, lo
             if (src[s]) {
 #pragma unroll
                 for (int c = 0; c < P; c += 4) {
-                    const f32x4_t q = *(const f32x4_t*)(src[s] + c);
+                    f32x4_t q = *(const f32x4_t*)(src[s] + c);
+                    const long slab = s < 2 ? slab_r : slab_c;
+                    for (int sp = 1; sp < splits; ++sp) q += *(const f32x4_t*)(src[s] + sp * slab + c);
                     add[c] += q[0]; add[c + 1] += q[1]; add[c + 2] += q[2]; add[c + 3] += q[3];
                 }
             }
@@ -469,8 +474,24 @@ int mte_pack_border_apply(void* y, long ldy, const float* corr_rows, const float
     if (!y || !corr_rows || !corr_cols || !Dt || !border_ok(B, H2, W2, Co, k, dtype) || ldy < Co || ldy % (dtype == MTE_DT_BF16 ? 8 : 4) != 0) return MTE_ERR_ARG;
     const int pad = k / 2, per16 = dtype == MTE_DT_BF16 ? 8 : 4;
     const int grid = bgrid((long)B * pb_border_count(H2, W2, pad) * (Co / per16));
-    if (dtype == MTE_DT_BF16) hipLaunchKernelGGL(border_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (bf16_t*)y, ldy, corr_rows, corr_cols, Dt, B, H2, W2, Co, pad);
-    else hipLaunchKernelGGL(border_apply_kernel<float>, dim3(grid), dim3(256), 0, stream, (float*)y, ldy, corr_rows, corr_cols, Dt, B, H2, W2, Co, pad);
+    if (dtype == MTE_DT_BF16) hipLaunchKernelGGL(border_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (bf16_t*)y, ldy, corr_rows, corr_cols, Dt, B, H2, W2, Co, pad, 1, 0L, 0L);
+    else hipLaunchKernelGGL(border_apply_kernel<float>, dim3(grid), dim3(256), 0, stream, (float*)y, ldy, corr_rows, corr_cols, Dt, B, H2, W2, Co, pad, 1, 0L, 0L);
+    return mte_check_launch();
+}
+
+// mte_pack_border_apply on the workspace of mte_pack_border_gemm_fwd: `splits` slabs per ring-line family (rows first), added in slab order inside the apply loop
+int mte_pack_border_apply_slabs(void* y, long ldy, const float* ws, int splits, const float* Dt, int B, int H2, int W2, int Co, int k, int dtype,
+                                hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!y || !ws || splits < 1 || splits > PBG_MAX_SPLITS || !Dt || !border_ok(B, H2, W2, Co, k, dtype) || ldy < Co || ldy % (dtype == MTE_DT_BF16 ? 8 : 4) != 0)
+        return MTE_ERR_ARG;
+    const int pad = k / 2, per16 = dtype == MTE_DT_BF16 ? 8 : 4;
+    const long slab_r = pb_gemm_slab_elems(0, B, H2, W2, Co, k), slab_c = pb_gemm_slab_elems(1, B, H2, W2, Co, k);
+    const float* cr = ws;
+    const float* cc = ws + splits * slab_r;
+    const int grid = bgrid((long)B * pb_border_count(H2, W2, pad) * (Co / per16));
+    if (dtype == MTE_DT_BF16) hipLaunchKernelGGL(border_apply_kernel<bf16_t>, dim3(grid), dim3(256), 0, stream, (bf16_t*)y, ldy, cr, cc, Dt, B, H2, W2, Co, pad, splits, slab_r, slab_c);
+    else hipLaunchKernelGGL(border_apply_kernel<float>, dim3(grid), dim3(256), 0, stream, (float*)y, ldy, cr, cc, Dt, B, H2, W2, Co, pad, splits, slab_r, slab_c);
     return mte_check_launch();
 }
 

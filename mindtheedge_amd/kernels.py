@@ -1477,6 +1477,38 @@ def _ring_gemm(x, wpack, cout, kh, kw, out_f32, flags=0):
     return out
 
 
+_ring_ws = {}               # (device, stream) -> fp32 scratch of the grouped forward ring GEMMs
+_ring_plan = {}             # (B, H2, W2, C16, co, k, dt) -> (workspace elements, slices), or None where the library does not take the grouped launch
+
+
+def _ring_terms_grouped(Rr, Rc, wr, wc, B, H2, W2, C16, co, k, dt):
+    """the forward ring terms of a folded pack layer by mte_pack_border_gemm_fwd: both ring-line families and both edges in ONE split-K launch.
+    -> (workspace of fp32 slabs, slices) for mte_pack_border_apply_slabs, or (None, 0) where the library answers MTE_ERR_UNSUPPORTED (the caller then runs
+    the two _ring_gemm launches).  The workspace follows _splitk_workspace: per-stream scratch (the apply that reads it is the next launch of the stream), a
+    fresh tensor while a graph is being captured."""
+    key = (B, H2, W2, C16, co, k, dt)
+    if key not in _ring_plan:
+        splits = ctypes.c_int(0)
+        n = int(lib.mte_pack_border_gemm_ws_elems(B, H2, W2, C16, co, k, dt, 0, ctypes.byref(splits)))
+        if n < 0 and n != -3:                                # (-3 = MTE_ERR_UNSUPPORTED, include/mte_kernels.h)
+            raise MteError("mte_pack_border_gemm_ws_elems failed: %s" % n)
+        _ring_plan[key] = (n, splits.value) if n > 0 and os.environ.get("MTE_NO_GROUPED_RING") != "1" else None
+    plan = _ring_plan[key]
+    if plan is None:
+        return None, 0
+    n, splits = plan
+    dev = Rr.device
+    if torch.cuda.is_current_stream_capturing():             # a graph keeps its own allocation alive (private pool)
+        ws = torch.empty((n,), dtype=torch.float32, device=dev)
+    else:
+        wkey = (str(dev), _stream())
+        ws = _ring_ws.get(wkey)
+        if ws is None or ws.numel() < n:
+            ws = _ring_ws[wkey] = torch.empty((n,), dtype=torch.float32, device=dev)
+    lib.mte_pack_border_gemm_fwd(Rr.data_ptr(), Rc.data_ptr(), wr.data_ptr(), wc.data_ptr(), ws.data_ptr(), ws.numel(), B, H2, W2, C16, co, k, dt, 0, _stream())
+    return ws, splits
+
+
 def _ring_wgrad(x, g, w):
     """fp32 OIHW gradient of a ring weight tensor w [N, 16C, kh, kw] from the ring line x and the gathered gradient g.  Not _conv_wgrad: that one may route a
     layer to the LDS-patch or nine-tap kernels, which are built and tested for square filters; a 1 x k / k x 1 filter takes the generic kernel (mte_conv2d_wgrad),
@@ -1485,6 +1517,10 @@ def _ring_wgrad(x, g, w):
     Bl, Cp, H, W = x.shape
     xp, ldx = _pl(x)
     gp, ldg = _pl(g)
+    if kw == 1 and W == 1:
+        # a column line [2B][H2][1][C] is the memory of a row line [2B][1][H2][C], a k x 1 filter on it a 1 x k filter with the same tap order (dw likewise):
+        # the kernel's pixel splits follow W, and as columns these launches ran at 23-68 TF against 61-106 as rows (profiles/pack_border_gemm_ab.txt)
+        H, W, kh, kw = 1, H, 1, kh
     per = cout * kh * kw * Cp
     cap = max(1, min(32, (96 << 20) // (4 * per)))
     stage = torch.empty((cap, cout, kh * kw, Cp), dtype=torch.float32, device=x.device)
@@ -1502,7 +1538,7 @@ class PackFoldedConvGnEluFn(torch.autograd.Function):
     between the two reference ops (layers01.py:237-238 vs :31), the folded form has seen conv3d's values outside the image; they
     depend on the data only on the one-pixel ring around it, so the exact result is the folded one plus a 1 x k convolution along
     the top / bottom ring rows, a k x 1 convolution along the left / right ring columns and a bias table over the pixel classes
-    (csrc/pack_border.hip).  Per pass: ring stencil + 2 GEMMs + apply (forward); gather + 2 GEMMs + ring data gradient (backward,
+    (csrc/pack_border.hip).  Per pass: ring stencil + one grouped split-K GEMM launch (csrc/pack_border_gemm.hip; fp32 mode: 2 GEMMs) + apply (forward); gather + 2 GEMMs + ring data gradient (backward,
     main queue); 2 weight-gradient GEMMs + scatter + ring weight gradient (backward, weight-gradient queue)."""
 
     @staticmethod
@@ -1527,10 +1563,14 @@ class PackFoldedConvGnEluFn(torch.autograd.Function):
         lib.mte_pack_ring_fwd(pp, ldp, w3c.data_ptr(), Rr.data_ptr(), Rc.data_ptr(), B, H2, W2, 4 * C, dt, _stream())
         wr, _ = f["pk_r"].get(f["Wr"], x.dtype, False)
         wc, _ = f["pk_c"].get(f["Wc"], x.dtype, False)
-        cr = _ring_gemm(Rr, wr, N, 1, k, True, _CONV_SOLO)
-        cc = _ring_gemm(Rc, wc, N, k, 1, True, _CONV_SOLO)
         yp, ldy = _pl(y)
-        lib.mte_pack_border_apply(yp, ldy, cr.data_ptr(), cc.data_ptr(), f["Dt"].data_ptr(), B, H2, W2, co, k, dt, _stream())
+        ws, splits = _ring_terms_grouped(Rr, Rc, wr, wc, B, H2, W2, 16 * C, co, k, dt)
+        if ws is not None:                                   # one grouped split-K launch; the slabs are added inside the apply loop
+            lib.mte_pack_border_apply_slabs(yp, ldy, ws.data_ptr(), splits, f["Dt"].data_ptr(), B, H2, W2, co, k, dt, _stream())
+        else:                                                # fp32 validation mode, shapes the grouped launch does not take
+            cr = _ring_gemm(Rr, wr, N, 1, k, True, _CONV_SOLO)
+            cc = _ring_gemm(Rc, wc, N, k, 1, True, _CONV_SOLO)
+            lib.mte_pack_border_apply(yp, ldy, cr.data_ptr(), cc.data_ptr(), f["Dt"].data_ptr(), B, H2, W2, co, k, dt, _stream())
         z, stats = _gn_forward(y, None, None, gamma, beta, GN_EPS, out=None if out is None else alias_of(out))
         ctx.save_for_backward(P, Rr, Rc, y, stats, w, w3c, b3c, gamma, beta, Wf)
         ctx.params = (w3, b3, b)
