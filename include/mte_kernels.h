@@ -471,6 +471,18 @@ int mte_sgd_step_ctl_dev(float* p, const float* g, float* buf, long n, const flo
  *   copy that does not read dst.  n = 0 returns 0 without a launch.  n < 0, a null pointer, a pointer that is not 16-byte aligned and
  *   overlapping ranges (equal pointers included) are MTE_ERR_ARG. */
 int mte_grad_accumulate(float* dst, const float* src, long n, int assign, mte_stream_t stream);
+/* ---- exponential moving average of the weights (csrc/optim.hip): streaming launches in mte_grad_accumulate's shape, no atomics, no state.
+ * mte_ema_update: ema[i] = d * ema[i] + omd * p[i] in fp32 -- two multiplications and one addition, each rounded once, in that order
+ *   (12 B per element: read, read, write); p is only read.
+ * mte_ema_update_dev: the same template on scal = {d, omd} read from DEVICE memory, bit-equal to the host form.  ctl may be null; otherwise
+ *   it is the word mte_grad_norm_clip leaves, and with ctl[1] != 0 the launch returns before its first load: the average keeps its bits
+ *   over a skipped step.  ctl[0] (the clip coefficient) is not read.  A null scal is MTE_ERR_ARG.
+ * mte_flat_swap: a[i] <-> b[i] bit for bit (16 B per element; NaN payloads survive: no arithmetic).
+ * All three: n = 0 returns 0 without a launch.  n < 0, a null pointer, a pointer that is not 16-byte aligned and overlapping ranges (equal
+ *   pointers included) are MTE_ERR_ARG. */
+int mte_ema_update(float* ema, const float* p, long n, float d, float omd, mte_stream_t stream);
+int mte_ema_update_dev(float* ema, const float* p, long n, const float* scal, const float* ctl, mte_stream_t stream);
+int mte_flat_swap(float* a, float* b, long n, mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

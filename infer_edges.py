@@ -233,12 +233,16 @@ def main():
     ap.add_argument('--split', action='store_true', help="the reference's loop: image and LiDAR columns of config.datasets.test.split[0], "
                     'the RGB and the RGB+LiDAR pass, colour maps and the three list files')
     ap.add_argument('--graph', action='store_true', help='replay the forward from a HIP graph (single frames are launch-bound)')
+    ap.add_argument('--ema', action='store_true', help="load the checkpoints' averaged weights ('state_dict_ema', written by a run with "
+                    'model.optimizer.ema_decay > 0) instead of the raw ones; a file without them is an error')
     args = ap.parse_args()
     import numpy as np
     import torch
     from mindtheedge_amd.utils.config import load_config
     from mindtheedge_amd.models.model_wrapper import ModelWrapper
     config = load_config(args.config)
+    if args.ema:
+        config.model.checkpoint_ema = config.model.depth_net.checkpoint_ema = True
     an = config.analysis or {}
     analyse = bool(an.get('run_heavy_edge_metrics') or an.get('run_metrics'))
     if analyse and (config.save or {}).get('folder'):

@@ -19,6 +19,9 @@
 //
 // Gradient accumulation: mte_grad_accumulate adds (or copies) one flat buffer into another in the same launch shape -- the micro-batch
 // sum of FusedFlatOptimizer(accumulate_grad_batches > 1).  It is a kernel of its own: nothing is added to the step kernels.
+//
+// Weight EMA: mte_ema_update / mte_ema_update_dev (ema = d * ema + omd * p, 12 B per element, after the step launch) and mte_flat_swap
+// (weights <-> average, bit for bit) in the same launch shape -- FusedFlatOptimizer(ema_decay > 0).  Kernels of their own as well.
 #include "common.hpp"
 #include "handoff.hpp"
 #include <cstdint>
@@ -260,9 +263,95 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_accumulate_kernel(float* __r
     }
 }
 
+// ---- exponential moving average of the weights -------------------------------------------------------------------------------------------
+// e[i] = d * e[i] + omd * p[i]: two fp32 multiplications and one fp32 addition, each rounded once, in that order (-ffp-contract=off), in
+// grad_accumulate_kernel's launch shape and with its 12 B per element (read e, read p, write e).  p is read-only.  DEV: {d, omd} come from
+// `scal` in device memory, and a non-null `ctl` (mte_grad_norm_clip's word) with ctl[1] set ends the kernel before its first load of e or
+// p -- the average keeps its bits over a skipped step, as p, m and v do.  ctl[0], the clip coefficient, is not the average's business.
+template <bool DEV>
+__global__ __launch_bounds__(OPT_THREADS) void ema_update_kernel(float* __restrict__ e, const float* __restrict__ p, long n, float d, float omd,
+                                                                 const float* __restrict__ scal, const float* __restrict__ ctl) {
+    if (DEV) {
+        if (ctl != nullptr && ctl[1] != 0.f) return;
+        d = scal[0]; omd = scal[1];
+    }
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        f32x4_t ee = ((const f32x4_t*)e)[i];
+        const f32x4_t pp = ((const f32x4_t*)p)[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) ee[k] = d * ee[k] + omd * pp[k];
+        ((f32x4_t*)e)[i] = ee;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        e[i] = d * e[i] + omd * p[i];
+    }
+}
+
+// ---- exchange of two flat buffers -------------------------------------------------------------------------------------------------------
+// a[i] <-> b[i] as 32-bit words (16 B per element: read both, write both): no arithmetic touches the values, so NaN payloads survive.
+__global__ __launch_bounds__(OPT_THREADS) void flat_swap_kernel(uint32_t* __restrict__ a, uint32_t* __restrict__ b, long n) {
+    typedef uint32_t u32x4_t __attribute__((ext_vector_type(4)));
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        const u32x4_t x = ((const u32x4_t*)a)[i], y = ((const u32x4_t*)b)[i];
+        ((u32x4_t*)a)[i] = y;
+        ((u32x4_t*)b)[i] = x;
+    }
+    if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+        const long i = (n4 << 2) + threadIdx.x;
+        const uint32_t x = a[i], y = b[i];
+        a[i] = y;
+        b[i] = x;
+    }
+}
+
+// mte_grad_accumulate's argument rules for two flat ranges of n floats: -> MTE_ERR_ARG, 0 with nothing to launch (n = 0), or 1
+inline int flat_pair_check(const void* a, const void* b, long n) {
+    const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+    if (!a || !b || n < 0 || ((x | y) & 15) || x == y) return MTE_ERR_ARG;
+    if (n == 0) return 0;
+    const uintptr_t bytes = (uintptr_t)n * sizeof(float);
+    if (x < y + bytes && y < x + bytes) return MTE_ERR_ARG;
+    return 1;
+}
+
 }  // namespace
 
 extern "C" {
+
+// Exponential moving average over flat fp32 buffers (16-byte aligned, disjoint): ema[i] = d * ema[i] + omd * p[i], three fp32 roundings in
+// that order; p is only read.  n = 0 launches nothing.  n < 0, a null or misaligned pointer and overlapping ranges (equal pointers
+// included) are MTE_ERR_ARG.
+int mte_ema_update(float* ema, const float* p, long n, float d, float omd, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    const int ok = flat_pair_check(ema, p, n);
+    if (ok <= 0) return ok;
+    hipLaunchKernelGGL(ema_update_kernel<false>, dim3(opt_grid(n >> 2)), dim3(OPT_THREADS), 0, stream, ema, p, n, d, omd, (const float*)nullptr,
+                       (const float*)nullptr);
+    return mte_check_launch();
+}
+
+// The same update with scal = {d, omd} in DEVICE memory (the launch is identical every step: it replays from a captured graph).  ctl may be
+// null; otherwise it is mte_grad_norm_clip's word, and with ctl[1] != 0 nothing is loaded or stored.  A null scal is MTE_ERR_ARG.
+int mte_ema_update_dev(float* ema, const float* p, long n, const float* scal, const float* ctl, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!scal) return MTE_ERR_ARG;
+    const int ok = flat_pair_check(ema, p, n);
+    if (ok <= 0) return ok;
+    hipLaunchKernelGGL(ema_update_kernel<true>, dim3(opt_grid(n >> 2)), dim3(OPT_THREADS), 0, stream, ema, p, n, 0.f, 0.f, scal, ctl);
+    return mte_check_launch();
+}
+
+// Exchange two flat fp32 buffers (16-byte aligned, disjoint) bit for bit in one launch; the argument rules of mte_ema_update.
+int mte_flat_swap(float* a, float* b, long n, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    const int ok = flat_pair_check(a, b, n);
+    if (ok <= 0) return ok;
+    hipLaunchKernelGGL(flat_swap_kernel, dim3(opt_grid(n >> 2)), dim3(OPT_THREADS), 0, stream, (uint32_t*)a, (uint32_t*)b, n);
+    return mte_check_launch();
+}
 
 // Gradient accumulation over flat fp32 buffers (16-byte aligned, disjoint): assign = 0 adds src into dst, dst[i] = dst[i] + src[i] with one
 // fp32 rounding; assign = 1 copies src's bits.  n = 0 launches nothing.  n < 0, a null or misaligned pointer and overlapping ranges

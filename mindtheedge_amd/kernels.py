@@ -1862,4 +1862,4 @@ def image_to_act(rgb, flip=False, dtype=None):
 
 
 # ---- the loss-side / optimizer-side bindings live in kernels_loss.py (round 6); re-exported so that `kernels.<name>` keeps working
-from .kernels_loss import EdgeLossFn, EdgeLossKindFn, BilinearResizeFn, DepthLossesFn, DepthLossesPairFn, SilogFn, SupervisedLossFn, NearestUpsampleFn, _EdgeScale, adam_step_flat, adamw_step_flat, sgd_step_flat, grad_norm_work, grad_norm_clip_flat, grad_accumulate_flat  # noqa: E402,F401
+from .kernels_loss import EdgeLossFn, EdgeLossKindFn, BilinearResizeFn, DepthLossesFn, DepthLossesPairFn, SilogFn, SupervisedLossFn, NearestUpsampleFn, _EdgeScale, adam_step_flat, adamw_step_flat, sgd_step_flat, grad_norm_work, grad_norm_clip_flat, grad_accumulate_flat, ema_update_flat, flat_swap  # noqa: E402,F401

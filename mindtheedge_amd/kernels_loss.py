@@ -414,6 +414,37 @@ def grad_accumulate_flat(dst, src, assign=False, stream=None):
     _K.lib.mte_grad_accumulate(dst.data_ptr(), src.data_ptr(), dst.numel(), int(bool(assign)), _K._stream() if stream is None else stream)
 
 
+def _flat_pair(name, a, b):
+    _K._require_gpu(a)
+    _K._require_gpu(b)
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.numel() != b.numel() or not (a.is_contiguous() and b.is_contiguous()):
+        raise MteError(name + " takes two contiguous float32 buffers of one size")
+
+
+def ema_update_flat(ema, p, scal, ctl=None, stream=None):
+    """ema <- d * ema + omd * p in fp32 (two multiplications and one addition, each rounded once) over two disjoint flat fp32 device
+    buffers of one size: ONE streaming launch.  ``scal`` = {d, omd}: two float32 values on the DEVICE, or a (d, omd) pair of Python
+    numbers for the host-scalar entry point (``ctl`` must then be None).  ``ctl``: mte_grad_norm_clip's word; with ctl[1] set the
+    launch leaves ``ema`` alone."""
+    _flat_pair("ema_update_flat", ema, p)
+    st = _K._stream() if stream is None else stream
+    if torch.is_tensor(scal):
+        _K._require_gpu(scal)
+        if scal.dtype != torch.float32 or scal.numel() < 2 or (ctl is not None and (ctl.dtype != torch.float32 or ctl.numel() < 2)):
+            raise MteError("ema_update_flat: scal holds two and ctl at least two float32 values")
+        _K.lib.mte_ema_update_dev(ema.data_ptr(), p.data_ptr(), ema.numel(), scal.data_ptr(), None if ctl is None else ctl.data_ptr(), st)
+    else:
+        if ctl is not None:
+            raise MteError("ema_update_flat: ctl goes with device scalars")
+        _K.lib.mte_ema_update(ema.data_ptr(), p.data_ptr(), ema.numel(), float(scal[0]), float(scal[1]), st)
+
+
+def flat_swap(a, b, stream=None):
+    """a <-> b bit for bit over two disjoint flat fp32 device buffers of one size: ONE streaming launch, no temporary"""
+    _flat_pair("flat_swap", a, b)
+    _K.lib.mte_flat_swap(a.data_ptr(), b.data_ptr(), a.numel(), _K._stream() if stream is None else stream)
+
+
 def grad_norm_work(n, device):
     """the zeroed work buffer of grad_norm_clip_flat for n gradient elements (records and ticket; allocate once, reuse every step)"""
     return torch.zeros((int(_K.lib.mte_grad_norm_work_bytes(int(n))) + 7) // 8, dtype=torch.float64, device=device)

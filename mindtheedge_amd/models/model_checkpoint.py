@@ -1,5 +1,5 @@
 """Checkpoint FORMAT of the reference (checkpoint half): packnet_sfm/models/model_checkpoint.py:71-81
-writes ``{'config', 'epoch', 'state_dict', 'optimizer', 'scheduler'}`` with ``state_dict`` keys ``model.depth_net.*`` and
+writes ``{'config', 'epoch', 'state_dict', 'optimizer', 'scheduler'}`` (+ ``'state_dict_ema'``, ``'ema'`` when the optimizer averages its weights) with ``state_dict`` keys ``model.depth_net.*`` and
 the optimizer layout of the configured torch class (``torch.optim.Adam`` / ``AdamW`` / ``SGD``); packnet_sfm/utils/load.py:117-201 reads it back (and TRI's published
 ``PackNetSAN01_*.ckpt`` files, whose extra sparse-branch tensors are skipped by the shape-checked, non-strict load in
 ``utils/load.py::load_network``).  ``save_checkpoint`` writes one file, ``load_checkpoint`` reads one; ``CheckpointPolicy`` is the
@@ -36,6 +36,17 @@ def save_checkpoint(filepath, model_wrapper):
         # every tensor of a state entry, whatever the optimizer keeps (Adam / AdamW: step, exp_avg, exp_avg_sq; SGD: momentum_buffer)
         ckpt['optimizer']['state'] = {i: {k: v.cpu() if torch.is_tensor(v) else v for k, v in st.items()}
                                       for i, st in ckpt['optimizer']['state'].items()}
+    opt = model_wrapper.optimizer
+    if opt is not None and getattr(opt, 'ema_decay', 0.0) > 0.0:
+        # a run that averages its weights: 'state_dict_ema' has the keys of 'state_dict' with every trained tensor taken from the average
+        # (buffers and untrained tensors are the raw file's), 'ema' the schedule's state.  'state_dict' stays the raw weights: the
+        # reference and every loader read the file as before, and a resume is exact.
+        averaged = opt.ema_named()
+        ckpt['state_dict_ema'] = dict(ckpt['state_dict'])
+        for k, p in model_wrapper.named_parameters():
+            if id(p) in averaged and k in ckpt['state_dict_ema']:
+                ckpt['state_dict_ema'][k] = averaged[id(p)].detach().cpu().clone()
+        ckpt['ema'] = opt.ema_state()
     torch.save(ckpt, filepath)
     return filepath
 

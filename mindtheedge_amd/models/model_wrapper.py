@@ -28,7 +28,7 @@ def set_random_seed(seed):
 def setup_depth_net(config, prepared, **kwargs):
     depth_net = load_class_args_create(config.name, paths=['networks.depth'], args={**config, **kwargs})
     if not prepared and config.checkpoint_path != '':
-        depth_net = load_network(depth_net, config.checkpoint_path, ['depth_net', 'disp_network'])
+        depth_net = load_network(depth_net, config.checkpoint_path, ['depth_net', 'disp_network'], ema=bool(config.get('checkpoint_ema')))
     return depth_net
 
 
@@ -51,7 +51,7 @@ def setup_model(config, prepared, **kwargs):
     if config.edges.train_depth_edges:
         model.add_edge_loss(setup_depth_edge_loss(config))
     if not prepared and config.model.checkpoint_path != '':
-        model = load_network(model, config.model.checkpoint_path, 'model')
+        model = load_network(model, config.model.checkpoint_path, 'model', ema=bool(config.model.get('checkpoint_ema')))
     if config.is_multi_gpu:
         raise NotImplementedError("nn.DataParallel is replaced by one process per GPU: launch with torch.distributed.run")
     return model
@@ -97,7 +97,9 @@ class ModelWrapper(nn.Module):
         one of that name and carries the bucketed RCCL gradient averaging when torch.distributed is initialised.
         config.model.optimizer.clip_grad_norm / skip_nonfinite_steps (this package's keys, beside `name`) switch on the device-side
         gradient-norm clipping and non-finite step guard of FusedFlatOptimizer; config.arch.accumulate_grad_batches > 1 its gradient
-        accumulation over micro-batches."""
+        accumulation over micro-batches; config.model.optimizer.ema_decay > 0 (with ema_warmup) its exponential moving average of the
+        weights, which Trainer.validate swaps in when ema_validate is set.  A resumed file's 'state_dict_ema' / 'ema' entries restore
+        the average and its update count; without them the average starts from the loaded weights at count 0."""
         import torch.distributed as dist
         from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedSGD, broadcast_parameters,
                                               reference_parameter_names)
@@ -128,7 +130,10 @@ class ModelWrapper(nn.Module):
         if accumulate is None:
             accumulate = self.config.arch.accumulate_grad_batches or 1
         optimizer = built[opt_cfg.name](flat, reducer=reducer, name='Depth', clip_grad_norm=float(opt_cfg.clip_grad_norm or 0.0),
-                                        skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), accumulate_grad_batches=accumulate, **kwargs)
+                                        skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), accumulate_grad_batches=accumulate,
+                                        ema_decay=float(opt_cfg.get('ema_decay') or 0.0),
+                                        ema_warmup=True if opt_cfg.get('ema_warmup') is None else bool(opt_cfg.get('ema_warmup')), **kwargs)
+        self.ema_validate = True if opt_cfg.get('ema_validate') is None else bool(opt_cfg.get('ema_validate'))
         optimizer.set_index_space(reference_parameter_names(self.depth_net), dict(self.depth_net.named_parameters()))
         sched = getattr(torch.optim.lr_scheduler, self.config.model.scheduler.name)
         scheduler = sched(optimizer, **filter_args(sched, self.config.model.scheduler))
@@ -137,6 +142,11 @@ class ModelWrapper(nn.Module):
                 optimizer.load_state_dict(self.resume['optimizer'])
             if 'scheduler' in self.resume:
                 scheduler.load_state_dict(self.resume['scheduler'])
+            if optimizer.ema_decay > 0.0 and 'state_dict_ema' in self.resume and 'ema' in self.resume:
+                # the averaged depth-network tensors under their reference names, as set_index_space numbers them
+                cut = 'depth_net.'
+                named = {k[k.find(cut) + len(cut):]: v for k, v in self.resume['state_dict_ema'].items() if cut in k}
+                optimizer.load_ema(named, self.resume['ema']['num_updates'])
         self.optimizer, self.scheduler = optimizer, scheduler
         return optimizer, scheduler
 

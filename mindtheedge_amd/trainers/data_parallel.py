@@ -63,6 +63,14 @@ class FlatParameters:
             self.accum = torch.zeros_like(self.grad)
         return self.accum
 
+    def enable_ema(self):
+        """``ema``: a flat fp32 buffer of ``total`` elements (+4 B per parameter) that holds the exponential moving average of ``flat``,
+        laid out like it; it starts as a bit copy of the weights as they stand.  The attribute exists only for an optimizer built with
+        ema_decay > 0."""
+        if getattr(self, 'ema', None) is None:
+            self.ema = self.flat.clone()
+        return self.ema
+
     def zero_grad(self):
         if self.grad.is_cuda:
             from .. import kernels as K
@@ -215,6 +223,18 @@ class BucketedAllReduce:
                 "launch_offsets_mb": [round(s * 4 / 2**20, 2) for _, s, _, _ in getattr(self, "last_launches", [])]}
 
 
+def ema_decay_pair(t, decay, warmup=True):
+    """(d32, omd32) of the t-th update (t = 1, 2, ...) of a weight EMA as Python floats that hold float32 values: d_t = min(decay,
+    (1 + t) / (10 + t)) with the warm-up, else decay, in double precision; d32 = float32(d_t), omd32 = float32(1 - double(d32))"""
+    import struct
+    f32 = lambda x: struct.unpack('f', struct.pack('f', x))[0]
+    d = float(decay)
+    if warmup:
+        d = min(d, (1.0 + t) / (10.0 + t))
+    d32 = f32(d)
+    return d32, f32(1.0 - d32)
+
+
 class FusedFlatOptimizer(torch.optim.Optimizer):
     """What the fused optimizers share: ONE HBM-bound kernel over the flat buffers per step, with everything around it -- the reducer's
     wait and its gradient scale, the gradient sink, the side stream, the weight-pack epoch and prefetch, the device error poll, the three
@@ -233,7 +253,8 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     tests and logging.  Across ranks the norm is taken after the all-reduce has finished, over the summed buffer with gscale = 1/world;
     all-reduce leaves the same bits on every rank, so every rank forms the same ``ctl`` and skips the same steps.
     Deviation from a host-side guard: the host cannot know that a step was skipped, so ``steps`` advances anyway -- Adam's bias
-    correction counts skipped steps, and SGD's first-step rule belongs to step 1 whether or not it was skipped.  Neither setting is
+    correction counts skipped steps, and SGD's first-step rule belongs to step 1 whether or not it was skipped; with a weight EMA
+    (below) ``ema_updates`` advances on a skipped step too, so the EMA's warm-up ramp counts skipped steps as well.  Neither setting is
     part of ``state_dict()``: they come from the configuration, not from the file.
 
     Gradient accumulation (``accumulate_grad_batches`` = k > 1): up to k micro-batches share one optimizer step, so that one card runs
@@ -249,13 +270,29 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     averaged gradient, and an inf or NaN in any micro-batch skips the step.  A group may be shorter than k (an epoch's end).  ``steps``
     advances once per step().  With k = 1 -- the default -- there is no buffer and no launch, and ``step()`` with nothing pending is the
     step described above bit for bit.  Neither the setting nor ``accum`` is part of ``state_dict()``: checkpoints are written where
-    no group is open."""
+    no group is open.
+
+    Weight EMA (``ema_decay`` = d in (0, 1)): ``FlatParameters.ema`` (+4 B per parameter, a bit copy of the weights at construction)
+    follows the weights by e <- d_t * e + (1 - d_t) * p, ONE mte_ema_update_dev launch (12 B per parameter) on the current stream right
+    after the step launch, once per step() and never per accumulate().  For the t-th update d_t = min(d, (1 + t) / (10 + t)) with
+    ``ema_warmup`` (early updates forget the random initialisation quickly) and d_t = d without.  The host forms d32 = float32(d_t) and
+    omd32 = float32(1 - double(d32)); ``advance()`` uploads both to ``ema_scal`` through a pinned ring of their own (``hyper`` stays three
+    floats), so the launch is the same every step and replays from a HIP graph.  The kernel computes two fp32 multiplications and one
+    fp32 addition per element, each rounded once (tests/ema_ref.py).  With a ``ctl`` the launch reads its skip flag: a skipped step leaves
+    the average's bits alone; the clip coefficient is not the average's business.  As with ``steps``, the host cannot know that a step
+    was skipped: ``ema_updates`` advances anyway, so the warm-up schedule counts skipped steps just as Adam's bias correction does.
+    ``ema_weights()`` swaps weights and average for validation; ``ema_state()`` / ``load_ema()`` / ``ema_named()`` carry the average to
+    and from checkpoints.  None of it is part of ``state_dict()``, which stays torch's layout.  With ema_decay = 0 -- the default --
+    there is no buffer, no scalar pair and no launch."""
 
     HAS_STEP = False                                         # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
     LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
     LOAD_KEYS = ('lr', 'initial_lr')
 
-    def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
+    def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1,
+                 ema_decay=0.0, ema_warmup=True):
+        if not 0.0 <= float(ema_decay) < 1.0:
+            raise ValueError("Invalid ema_decay value: {} (in [0, 1); 0 = off)".format(ema_decay))
         if not float(clip_grad_norm) >= 0.0:
             raise ValueError("Invalid clip_grad_norm value: {} (0 = off)".format(clip_grad_norm))
         if int(accumulate_grad_batches) != accumulate_grad_batches or int(accumulate_grad_batches) < 1:
@@ -279,6 +316,13 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             if flat.flat.is_cuda:
                 from .. import kernels as K
                 self._norm_work = K.grad_norm_work(flat.grad.numel(), flat.flat.device)
+        self.ema_decay, self.ema_warmup = float(ema_decay), bool(ema_warmup)
+        self.ema_updates = 0                                  # updates of the average so far (t of the decay schedule)
+        if self.ema_decay > 0.0:
+            # only then: the default optimizer has no average, no `ema_scal` and no EMA launch
+            flat.enable_ema()
+            self.ema_scal = torch.zeros(2, dtype=torch.float32, device=flat.flat.device)     # {d32, omd32}, read by the kernel
+            self._ema_pinned = None
 
     def grad_stats(self):
         """{'grad_norm', 'clip_coef', 'skipped', 'skipped_steps'} of the last step as Python numbers: ONE host read (it waits for the
@@ -363,6 +407,8 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             else:
                 self._norm_clip(K, float(gscale), stream)
                 self._launch_ctl(K, g, float(gscale), stream)
+            if self.ema_decay > 0.0:                         # the average follows the weights the step just wrote (or, skipped, left alone)
+                K.ema_update_flat(self.flatp.ema, self.flatp.flat, self.ema_scal, getattr(self, 'ctl', None), stream)
             K.bump_weights_epoch()
         else:
             self.steps += 1
@@ -396,6 +442,93 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             self._hyper_events[i] = ev
         else:
             self.hyper.copy_(torch.tensor(vals, dtype=torch.float32), non_blocking=True)
+        if self.ema_decay > 0.0:
+            self.ema_updates += 1
+            pair = ema_decay_pair(self.ema_updates, self.ema_decay, self.ema_warmup)
+            if self.ema_scal.is_cuda:
+                # a pinned ring of its own, as hyper's: each slot waits for its last upload before it is rewritten
+                if self._ema_pinned is None:
+                    self._ema_pinned = torch.empty((16, 2), dtype=torch.float32).pin_memory()
+                    self._ema_events = [None] * 16
+                i = self.ema_updates % 16
+                if self._ema_events[i] is not None:
+                    self._ema_events[i].synchronize()
+                slot = self._ema_pinned[i]
+                slot[0], slot[1] = pair
+                self.ema_scal.copy_(slot, non_blocking=True)
+                ev = self._ema_events[i] or torch.cuda.Event()
+                ev.record()
+                self._ema_events[i] = ev
+            else:
+                self.ema_scal.copy_(torch.tensor(pair, dtype=torch.float32))
+
+    def _swap_ema(self):
+        """flat <-> ema behind every queued reader of the parameters, then packs for the new weights"""
+        from .. import kernels as K
+        flat = self.flatp
+        if flat.flat.is_cuda:
+            K.join_side_stream()
+            cur = torch.cuda.current_stream()
+            for st in K._side["streams"]:                     # the weight-pack launches of prefetch_weight_packs() (see ema_weights)
+                cur.wait_stream(st)
+            K.flat_swap(flat.flat, flat.ema)
+            K.bump_weights_epoch()
+            K.prefetch_weight_packs()
+        else:                                                 # host buffers: no kernel, the same exchange
+            held = flat.flat.clone()
+            flat.flat.copy_(flat.ema)
+            flat.ema.copy_(held)
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with optimizer.ema_weights():`` -- inside the block every trained tensor holds the AVERAGE (validation, top-k ranking,
+        inference) and ``flat.ema`` holds the raw weights; on exit both are back bit for bit.  One mte_flat_swap launch each way: no
+        second network, no temporary buffer, no host read.
+
+        Ordering.  prefetch_weight_packs() queues pack launches on the side stream that READ the parameters.  ``join_side_stream()``
+        waits only while the weight-gradient launches have marked the side streams dirty (``_side["dirty"]``); the prefetch does
+        not set that mark, so the join alone does not cover it.  The current stream is therefore made to wait for every stream in
+        ``_side["streams"]`` itself (``wait_stream``) before the swap launch -- on entry and again on exit, where the packs that the
+        block's own prefetch queued read the average.  Then the weights epoch is bumped and the packs are prefetched from the
+        swapped-in weights, as after a step.
+
+        Raises RuntimeError with an accumulation group open (the gradients in ``accum`` belong to the raw weights) and under stream
+        capture (the swap is not part of a training step's graph)."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("ema_weights() needs an optimizer built with ema_decay > 0")
+        if self._pending > 0:
+            raise RuntimeError("ema_weights() with an accumulation group open ({} micro-batches pending): step() first".format(self._pending))
+        if self.flatp.flat.is_cuda and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("ema_weights() under stream capture: the swap is not part of a captured step")
+        self._swap_ema()
+        try:
+            yield self
+        finally:
+            self._swap_ema()
+
+    def ema_state(self):
+        """what a checkpoint keeps of the average beside its tensors"""
+        return {'decay': self.ema_decay, 'warmup': self.ema_warmup, 'num_updates': self.ema_updates}
+
+    def ema_named(self):
+        """{id(parameter): the average of that tensor, a view into ``flat.ema``} for every trained tensor"""
+        flat = self.flatp
+        return {id(p): flat.ema[o:o + p.numel()].view(p.shape) for p, o in zip(flat.params, flat.offsets)}
+
+    @torch.no_grad()
+    def load_ema(self, named_tensors, num_updates):
+        """Fill ``flat.ema`` from {reference parameter name: tensor} through the index space of set_index_space and set the update
+        count.  A trained tensor the dictionary does not name keeps what the average holds (the weights it was built from)."""
+        if self.ema_decay <= 0.0:
+            raise RuntimeError("load_ema() needs an optimizer built with ema_decay > 0")
+        for name, p, o in self._space():
+            if p is None or name is None or name not in named_tensors:
+                continue
+            t = named_tensors[name]
+            if tuple(t.shape) != tuple(p.shape):
+                raise ValueError("averaged tensor {} has shape {}, parameter has {}".format(name, tuple(t.shape), tuple(p.shape)))
+            self.flatp.ema[o:o + p.numel()].copy_(t.reshape(-1))
+        self.ema_updates = int(num_updates)
 
     def set_index_space(self, names, local_names):
         """Number the optimizer state like the reference's ``torch.optim.<name>(depth_net.parameters())`` does.
@@ -502,13 +635,15 @@ class FusedAdam(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'betas', 'eps', 'initial_lr', 'weight_decay', 'decoupled_weight_decay')
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
-                 decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
+                 decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0,
+                 ema_warmup=True):
         if not 0.0 <= float(weight_decay):
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
         super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                     capturable=False, differentiable=False, fused=None,
                                     decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name,
-                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches)
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
+                         ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
 
@@ -558,14 +693,15 @@ class FusedSGD(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
 
     def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth',
-                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1):
+                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True):
         if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
             raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
         if nesterov and (momentum <= 0 or dampening != 0):
             raise ValueError("Nesterov momentum requires a momentum and zero dampening")
         super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                     maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name,
-                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches)
+                         clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
+                         ema_decay=ema_decay, ema_warmup=ema_warmup)
         self.momentum_buffer = None
         self.state_buffers()
 

@@ -3,6 +3,7 @@
 checkpoint=None).fit(module)``, ``proc_rank``, ``world_size``, ``is_rank_0``.  The inner loop is the reference's
 zero_grad -> to-device -> training_step -> backward -> optimizer.step, minus its 4-6 ``.item()`` host syncs per step:
 running means are accumulated on the device and read once per ``log_every`` steps."""
+import contextlib
 import os
 
 import torch
@@ -125,9 +126,14 @@ class Trainer:
         was_training = module.training
         module.eval()
         results = []
-        for n, dataloader in enumerate(dataloaders):
-            outputs = [module.validation_step(sample_to_cuda(batch, self.device), i, n) for i, batch in enumerate(dataloader)]
-            results.append(module.validation_epoch_end(outputs, n))
+        # an optimizer that keeps a weight EMA (model.optimizer.ema_decay > 0) validates on the average unless ema_validate is off: the
+        # block swaps the average in and the raw weights back (FusedFlatOptimizer.ema_weights), so the checkpoint policy ranks epochs by it
+        opt = getattr(module, 'optimizer', None)
+        averaged = opt is not None and getattr(opt, 'ema_decay', 0.0) > 0.0 and getattr(module, 'ema_validate', True)
+        with (opt.ema_weights() if averaged else contextlib.nullcontext()):
+            for n, dataloader in enumerate(dataloaders):
+                outputs = [module.validation_step(sample_to_cuda(batch, self.device), i, n) for i, batch in enumerate(dataloader)]
+                results.append(module.validation_epoch_end(outputs, n))
         module.train(was_training)
         return results
 

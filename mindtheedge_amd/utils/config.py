@@ -23,19 +23,23 @@ _DEFAULTS = {
     # (8 per GPU x N GPUs); k > 1 runs that effective batch on fewer cards (FusedFlatOptimizer.accumulate).  1 = every batch steps.
     'arch': {'seed': 42, 'min_epochs': 1, 'max_epochs': 50, 'validate_first': False, 'accumulate_grad_batches': 1},
     'model': {
-        'name': 'SemiSupEdgeModel', 'checkpoint_path': '',
+        # checkpoint_ema (here and under depth_net): load checkpoint_path's averaged weights ('state_dict_ema') instead of the raw ones
+        'name': 'SemiSupEdgeModel', 'checkpoint_path': '', 'checkpoint_ema': False,
         # name: 'Adam', 'AdamW' or 'SGD' (default_config.py: model.optimizer.name).  depth: the keys torch.optim.<name> accepts reach the fused
         # optimizer -- lr, weight_decay, betas, eps (Adam, AdamW); lr, weight_decay, momentum, dampening, nesterov (SGD); amsgrad / maximize: true
         # are not built (ModelWrapper.configure_optimizers).  clip_grad_norm (0 = off): torch.nn.utils.clip_grad_norm_'s max_norm over all trained
         # tensors; skip_nonfinite_steps: a step whose gradient holds an inf or a NaN changes nothing.  Both are this package's own keys and sit
         # beside `name`, not under `depth`, so filter_args never hands them to torch.optim; both off = the step as it always was.
-        'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}, 'clip_grad_norm': 0.0, 'skip_nonfinite_steps': False},
+        # ema_decay (0 = off): FusedFlatOptimizer keeps an exponential moving average of the trained tensors with that decay (ema_warmup: the
+        # decay of the t-th update is min(ema_decay, (1 + t) / (10 + t))); ema_validate: validation, and with it save_top_k, runs on the average.
+        'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}, 'clip_grad_norm': 0.0, 'skip_nonfinite_steps': False,
+                      'ema_decay': 0.0, 'ema_warmup': True, 'ema_validate': True},
         'scheduler': {'name': 'StepLR', 'step_size': 10, 'gamma': 0.5},
         'params': {'crop': '', 'min_depth': 0.0, 'max_depth': 80.0, 'scale_output': 'resize'},     # default_config.py:84-87
         'loss': {'supervised_method': 'sparse-l1', 'supervised_num_scales': 4, 'supervised_loss_weight': 0.9,
                  'depth_edges_loss_weight': 1.0, 'edges_depth_edge_loss_all_scales': False, 'upsample_depth_maps': False,
                  'flip_lr_prob': 0.5, 'progressive_scaling': 0.0},
-        'depth_net': {'name': 'PackNetSAN01', 'checkpoint_path': '', 'version': '1A', 'dropout': 0.0,
+        'depth_net': {'name': 'PackNetSAN01', 'checkpoint_path': '', 'checkpoint_ema': False, 'version': '1A', 'dropout': 0.0,
                       'freeze_encoder': False, 'freeze_decoder': False, 'freeze_san': False, 'input_channels': 3,
                       'is_depth_aux_net': False, 'output_channels': 1},
     },

@@ -112,6 +112,9 @@ class GraphedTrainStep:
                 "buffers": [(b, b.detach().clone()) for b in self.model.buffers()]}
         if flat is not None:
             snap.update(flat=flat.flat.clone(), state=[(b, b.clone()) for _, b in opt.state_buffers()], steps=opt.steps)
+            if getattr(flat, "ema", None) is not None:      # an averaging optimizer: the warm-up steps move the average and its count too
+                snap["state"].append((flat.ema, flat.ema.clone()))
+                snap["ema_updates"] = opt.ema_updates
         else:
             import copy
             snap.update(params=[(p, p.detach().clone()) for g in opt.param_groups for p in g["params"]],
@@ -128,6 +131,8 @@ class GraphedTrainStep:
                 for b, v in snap["state"]:                  # Adam's moments / SGD's momentum buffer
                     b.copy_(v)
                 opt.steps = snap["steps"]
+                if "ema_updates" in snap:
+                    opt.ema_updates = snap["ema_updates"]
             else:
                 for p, v in snap["params"]:
                     p.copy_(v)

@@ -107,8 +107,9 @@ def backwards_state_dict(state_dict):
     return out
 
 
-def load_network(network, path, prefixes=''):
-    """Prefix-stripped, shape-checked, non-strict checkpoint load (reference load.py:117-166).
+def load_network(network, path, prefixes='', ema=False):
+    """Prefix-stripped, shape-checked, non-strict checkpoint load (reference load.py:117-166).  ``ema``: read the file's averaged weights
+    ('state_dict_ema', written when the run kept a weight EMA) instead of 'state_dict'; a file without them raises KeyError.
 
     As upstream, a prefix matches ANYWHERE in a key (`prefix + '.' in key`: `module.model.depth_net.conv1.weight` loads with
     prefix `depth_net`) and everything up to and including its first occurrence is cut; the cut key is what the next prefix of the
@@ -116,7 +117,12 @@ def load_network(network, path, prefixes=''):
     prefixes = make_list(prefixes)
     if isinstance(path, str):
         ckpt = read_checkpoint(path)
-        sd = ckpt.get('state_dict', ckpt)
+        if ema:
+            if 'state_dict_ema' not in ckpt:
+                raise KeyError("{} holds no averaged weights ('state_dict_ema'): it was written without model.optimizer.ema_decay".format(path))
+            sd = ckpt['state_dict_ema']
+        else:
+            sd = ckpt.get('state_dict', ckpt)
         if path.endswith('.pth.tar'):
             sd = backwards_state_dict(sd)
     else:                                        # a state dict (reference :139-140: the resume path passes one)
