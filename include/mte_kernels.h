@@ -483,6 +483,31 @@ int mte_grad_accumulate(float* dst, const float* src, long n, int assign, mte_st
 int mte_ema_update(float* ema, const float* p, long n, float d, float omd, mte_stream_t stream);
 int mte_ema_update_dev(float* ema, const float* p, long n, const float* scal, const float* ctl, mte_stream_t stream);
 int mte_flat_swap(float* a, float* b, long n, mte_stream_t stream);
+/* ---- per-tensor learning-rate and weight-decay multipliers (csrc/optim.hip): the SEG form of the device-scalar steps.  The flat buffers
+ * align every tensor to 64 elements, so an aligned 64-element block belongs to one tensor.
+ *   block_class[b] (DEVICE memory, n / 64 bytes): the class of elements 64 b .. 64 b + 63; a byte >= n_classes is read as n_classes - 1.
+ *   class_scales (DEVICE memory, 2 * n_classes floats): {lr_mult, wd_mult} per class, 1 <= n_classes <= 16.
+ *   For class c: lr_c = float32(hyper[0] * lr_mult_c), wd_c = float32(weight_decay * wd_mult_c); every block is updated by the plain
+ *   step's arithmetic with its class's pair, and wd_c == 0 takes the no-decay arithmetic (not `+ 0 * p`): the result equals, slice by
+ *   slice and bit for bit, mte_adamw_step_dev / mte_sgd_step_dev on that slice with {lr_c, wd_c}.
+ *   ctl may be null; non-null it is mte_grad_norm_clip's word with the meaning it has in the _ctl_dev forms.
+ *   n % 64 != 0, a null table, n_classes out of range and the plain forms' argument errors are MTE_ERR_ARG. */
+int mte_adamw_step_seg_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                           float weight_decay, int decoupled, float gscale, const unsigned char* block_class, const float* class_scales,
+                           int n_classes, const float* ctl, mte_stream_t stream);
+int mte_sgd_step_seg_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
+                         float gscale, const unsigned char* block_class, const float* class_scales, int n_classes, const float* ctl,
+                         mte_stream_t stream);
+/* ---- per-tensor statistics of the flat gradient and weights (csrc/optim.hip): ONE read-only launch however many tensors there are.
+ *   g, p: flat fp32 buffers of n elements, 16-byte aligned; p may be null.  Tensor t is elements seg_begin[t] .. seg_begin[t] +
+ *   seg_numel[t] - 1 (`long` arrays of T entries in DEVICE memory; begins are multiples of 64, the padding behind a tensor is not read;
+ *   1 <= T <= 4096).  out (DEVICE memory, 4 * T doubles): per tensor {sum g^2, max |g| over the finite elements (0 without one), the
+ *   count of inf / NaN elements of g, sum p^2 (0 without p)}; the sums are fp64 (squares exact, additions rounded) in an order that the
+ *   table alone fixes: bit-equal call to call and under graph replay.  A range that leaves [0, n) reads nothing and reports zeros.
+ *   `work`: mte_tensor_stats_work_bytes(n, T) bytes, 16-byte aligned, zeroed ONCE by the caller (tickets that return to zero, records). */
+long mte_tensor_stats_work_bytes(long n, int T);
+int mte_tensor_stats(const float* g, const float* p, long n, const long* seg_begin, const long* seg_numel, int T, void* work, double* out,
+                     mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

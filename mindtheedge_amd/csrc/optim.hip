@@ -22,6 +22,12 @@
 //
 // Weight EMA: mte_ema_update / mte_ema_update_dev (ema = d * ema + omd * p, 12 B per element, after the step launch) and mte_flat_swap
 // (weights <-> average, bit for bit) in the same launch shape -- FusedFlatOptimizer(ema_decay > 0).  Kernels of their own as well.
+//
+// Per-tensor learning-rate and weight-decay multipliers: the SEG form of the device-scalar steps (mte_adamw_step_seg_dev,
+// mte_sgd_step_seg_dev) reads one class byte per aligned 64-element block of the flat buffers and {lr_mult, wd_mult} per class --
+// FusedFlatOptimizer(tensor_scales=...).  Kernels of their own: adamw_kernel / sgd_kernel and their instances are what they were.
+// Per-tensor gradient statistics: mte_tensor_stats, one read-only launch over the gradient (and the weights) with the tensor table in
+// device memory, fp64 sums in an order fixed by that table.
 #include "common.hpp"
 #include "handoff.hpp"
 #include <cstdint>
@@ -242,6 +248,288 @@ __global__ __launch_bounds__(OPT_THREADS) void grad_norm_kernel(NormArgs a) {
     if (skip) a.ctl[3] = a.ctl[3] + 1.f;
 }
 
+// ---- the SEG form: per-tensor learning-rate and weight-decay multipliers --------------------------------------------------------------------
+// FlatParameters aligns every tensor to 64 elements, so an aligned 64-element block of the flat buffers belongs to ONE tensor.  cls[b] is
+// the class of elements 64 b .. 64 b + 63 (n / 64 bytes), scales = {lr_mult, wd_mult} per class (2 * n_classes floats); both are launch
+// constants in device memory.  For class c: lr_c = lr * lr_mult_c and wd_c = wd * wd_mult_c, ONE fp32 multiplication each, lr the step's
+// own hyper[0]; the element update is adam_elem / sgd_elem above with lr_c for lr and wd_c for wd (AdamW's lrwd = lr_c * wd_c).  A class
+// whose wd_c is exactly 0 takes the no-decay instance of the element update (never `+ 0 * p`), as the plain launchers do for
+// weight_decay = 0: a SEG launch equals, slice by slice and bit for bit, the plain launch on that slice with {lr_c, wd_c}.
+// The table {lr_c, wd_c} is staged in LDS by the first n_classes threads (<= 16 entries: no by-value array, no scratch); a thread reads
+// its vector's class byte (16 consecutive threads share it: a vector never straddles a block, and n % 64 == 0 leaves no tail) and then
+// the pair, a broadcast or a few-way LDS read.  A byte >= n_classes is clamped to the last class.  ctl may be null (a uniform branch).
+constexpr int SEG_MAX_CLASSES = 16;
+struct SegArgs { const uint8_t* cls; const float* scales; const float* ctl; int n_classes; };
+
+template <int WD>
+__global__ __launch_bounds__(OPT_THREADS) void adamw_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                                float* __restrict__ v, long n, const float* __restrict__ hyper, AdamScalars s,
+                                                                SegArgs t) {
+    __shared__ float s_lr[SEG_MAX_CLASSES], s_wd[SEG_MAX_CLASSES];
+    if (t.ctl != nullptr) {                                // as adamw_kernel's CTL form: the skip flag first, before any load
+        if (t.ctl[1] != 0.f) return;
+        s.gscale = s.gscale * t.ctl[0];
+    }
+    s.lr = hyper[0]; s.bc1 = hyper[1]; s.bc2s = hyper[2];
+    if ((int)threadIdx.x < t.n_classes) {
+        s_lr[threadIdx.x] = s.lr * t.scales[2 * threadIdx.x];
+        s_wd[threadIdx.x] = s.wd * t.scales[2 * threadIdx.x + 1];
+    }
+    __syncthreads();
+    const int last = t.n_classes - 1;
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        int c = t.cls[i >> 4];
+        c = c > last ? last : c;
+        AdamScalars sc = s;
+        sc.lr = s_lr[c]; sc.wd = s_wd[c];
+        f32x4_t pp = ((f32x4_t*)p)[i], gg = ((const f32x4_t*)g)[i], mm = ((f32x4_t*)m)[i], vv = ((f32x4_t*)v)[i];
+        if (WD != WD_NONE && sc.wd != 0.f) {
+            const float lrwd = sc.lr * sc.wd;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pp[k], mk = mm[k], vk = vv[k];
+                adam_elem<WD>(pk, gg[k], mk, vk, sc, lrwd);
+                pp[k] = pk; mm[k] = mk; vv[k] = vk;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pp[k], mk = mm[k], vk = vv[k];
+                adam_elem<WD_NONE>(pk, gg[k], mk, vk, sc, 0.f);
+                pp[k] = pk; mm[k] = mk; vv[k] = vk;
+            }
+        }
+        ((f32x4_t*)p)[i] = pp; ((f32x4_t*)m)[i] = mm; ((f32x4_t*)v)[i] = vv;
+    }
+}
+
+template <int MOM, bool WD>
+__global__ __launch_bounds__(OPT_THREADS) void sgd_seg_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ buf, long n,
+                                                              const float* __restrict__ hyper, SgdScalars s, SegArgs t) {
+    __shared__ float s_lr[SEG_MAX_CLASSES], s_wd[SEG_MAX_CLASSES];
+    if (t.ctl != nullptr) {                                // as sgd_kernel's CTL form
+        if (t.ctl[1] != 0.f) return;
+        s.gscale = s.gscale * t.ctl[0];
+    }
+    s.lr = hyper[0]; s.mu_eff = hyper[1]; s.omd_eff = hyper[2];
+    if ((int)threadIdx.x < t.n_classes) {
+        s_lr[threadIdx.x] = s.lr * t.scales[2 * threadIdx.x];
+        s_wd[threadIdx.x] = s.wd * t.scales[2 * threadIdx.x + 1];
+    }
+    __syncthreads();
+    const int last = t.n_classes - 1;
+    const long n4 = n >> 2;
+    for (long i = blockIdx.x * (long)blockDim.x + threadIdx.x; i < n4; i += (long)gridDim.x * blockDim.x) {
+        int c = t.cls[i >> 4];
+        c = c > last ? last : c;
+        SgdScalars sc = s;
+        sc.lr = s_lr[c]; sc.wd = s_wd[c];
+        f32x4_t pp = ((f32x4_t*)p)[i], gg = ((const f32x4_t*)g)[i], bb = {0.f, 0.f, 0.f, 0.f};
+        if (MOM != MOM_NONE) bb = ((f32x4_t*)buf)[i];
+        if (WD && sc.wd != 0.f) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pp[k], bk = bb[k];
+                sgd_elem<MOM, true>(pk, gg[k], bk, sc);
+                pp[k] = pk; bb[k] = bk;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float pk = pp[k], bk = bb[k];
+                sgd_elem<MOM, false>(pk, gg[k], bk, sc);
+                pp[k] = pk; bb[k] = bk;
+            }
+        }
+        ((f32x4_t*)p)[i] = pp;
+        if (MOM != MOM_NONE) ((f32x4_t*)buf)[i] = bb;
+    }
+}
+
+template <int MOM>
+void sgd_seg_launch_wd(float* p, const float* g, float* buf, long n, const float* hyper, const SgdScalars& s, const SegArgs& t, hipStream_t stream) {
+    const dim3 grid(opt_grid(n >> 2)), block(OPT_THREADS);
+    if (s.wd != 0.f) hipLaunchKernelGGL((sgd_seg_kernel<MOM, true>), grid, block, 0, stream, p, g, buf, n, hyper, s, t);
+    else hipLaunchKernelGGL((sgd_seg_kernel<MOM, false>), grid, block, 0, stream, p, g, buf, n, hyper, s, t);
+}
+
+// ---- per-tensor statistics of the flat gradient (and weights) ------------------------------------------------------------------------------
+// One read-only launch.  Tensor t is elements [begin_t, begin_t + numel_t) of the flat buffers (begin_t a multiple of 64; the padding
+// behind numel_t is never read).  out[4 t ..] = {S_g = sum g^2, amax_g = max |g| over the finite elements (0 without one), the count of
+// non-finite elements of g, S_p = sum p^2 (0 without p)}, all fp64; the squares are exact there, only the additions round, and an inf
+// or a NaN reaches S_g (inf^2 = inf).
+// Order of the additions, a function of the tensor table alone -- not of the grid, not of arrival:
+//   * a tensor is cut from its start into chunks of STAT_CHUNK elements (the last one ragged; an empty tensor has one empty chunk);
+//     chunk k of tensor t has the global index first_t + k, first_t the running sum of the chunk counts (every workgroup forms that
+//     table in LDS: T <= STAT_MAX_T);
+//   * a chunk is read by ONE workgroup: thread j adds the vectors j, j + 256, ... of the chunk in that order (loads are issued ahead of
+//     their additions), then thread j < (numel & 3) of the last chunk the tensor's j-th trailing element; the 256 partials fold in
+//     a fixed tree (down each 64-lane wave by halving strides, then the four waves in index order) into ONE record of four fp64 values;
+//   * a tensor of one chunk is finished there.  Otherwise the workgroup draws the TENSOR's ticket (handoff.hpp, as grad_norm_kernel),
+//     and the one that draws the last of its chunk_count tickets adds the records: thread j the records j, j + 256, ... in that order,
+//     then the same tree.  Workgroups take chunks c = workgroup, workgroup + grid, ...: every loop is bounded and nobody waits.
+// Tickets go back to zero, so the launch replays from a captured graph and is bit-equal call to call.
+// work = {tickets[T] (unsigned, padded to 16 B), records[n / STAT_CHUNK + T][4] fp64}, zeroed once by the caller.
+constexpr long STAT_CHUNK = 32768;                          // elements: 128 KB of gradient per record (77.0 M elements: 2350 + 218 chunks)
+constexpr int STAT_CAP = 1024;                              // workgroups
+constexpr int STAT_MAX_T = 4096;
+constexpr int STAT_UNROLL = 4;
+inline long stat_max_chunks(long n, long T) { return n / STAT_CHUNK + T; }
+inline long stat_ticket_bytes(long T) { return (4 * T + 15) / 16 * 16; }
+
+struct StatArgs {
+    const float* g; const float* p; long n;
+    const long* begin; const long* numel; int T; int fences;
+    long max_chunks;
+    unsigned* tickets; double* records; double* out;
+};
+
+struct StatAcc { double sg, amax, nf, sp; };
+
+__device__ __forceinline__ void stat_add_g(StatAcc& a, float x) {
+    a.sg += (double)x * (double)x;
+    const float ax = fabsf(x);
+    if (ax <= 3.402823466e+38f) a.amax = fmax(a.amax, (double)ax);
+    else a.nf += 1.0;                                      // inf or NaN (the comparison is false for a NaN)
+}
+
+// the workgroup's 256 partials -> thread 0's `a`, in a fixed tree; sh: 4 waves x 4 values.  Every thread calls it.
+__device__ __forceinline__ void stat_fold(StatAcc& a, double (*sh)[4]) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        a.sg += __shfl_down(a.sg, off, 64);
+        a.amax = fmax(a.amax, __shfl_down(a.amax, off, 64));
+        a.nf += __shfl_down(a.nf, off, 64);
+        a.sp += __shfl_down(a.sp, off, 64);
+    }
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) { sh[tid >> 6][0] = a.sg; sh[tid >> 6][1] = a.amax; sh[tid >> 6][2] = a.nf; sh[tid >> 6][3] = a.sp; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < OPT_THREADS / 64; ++w) {
+            a.sg += sh[w][0]; a.amax = fmax(a.amax, sh[w][1]); a.nf += sh[w][2]; a.sp += sh[w][3];
+        }
+    }
+    __syncthreads();                                       // sh may be written again
+}
+
+template <bool WITH_P>
+__global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(StatArgs a) {
+    __shared__ int s_first[STAT_MAX_T + 1];                // s_first[t]: global index of tensor t's first chunk; s_first[T]: all chunks
+    __shared__ int s_part[OPT_THREADS];
+    __shared__ double s_fold[OPT_THREADS / 64][4];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, T = a.T;
+    constexpr int PER = STAT_MAX_T / OPT_THREADS;          // consecutive tensors per thread in the scan
+
+    // chunk counts and their running sum.  A tensor whose range leaves [0, n) counts as empty: nothing outside the buffers is read.
+    int cnt[PER], mine = 0;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = tid * PER + k;
+        int c = 0;
+        if (t < T) {
+            const long b = a.begin[t], m = a.numel[t];
+            const bool ok = b >= 0 && m > 0 && (b & 3) == 0 && b <= a.n && m <= a.n - b;
+            c = ok ? (int)((m + STAT_CHUNK - 1) / STAT_CHUNK) : 1;
+        }
+        cnt[k] = c;
+        mine += c;
+    }
+    s_part[tid] = mine;
+    __syncthreads();
+    for (int st = 1; st < OPT_THREADS; st <<= 1) {         // inclusive scan of the 256 partials
+        const int add = tid >= st ? s_part[tid - st] : 0;
+        __syncthreads();
+        s_part[tid] += add;
+        __syncthreads();
+    }
+    int run = s_part[tid] - mine;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        const int t = tid * PER + k;
+        if (t <= T) s_first[t] = run;
+        run += cnt[k];
+    }
+    if (tid == OPT_THREADS - 1) s_first[STAT_MAX_T] = run; // T = STAT_MAX_T: no thread owns index T
+    __syncthreads();
+    long total = s_first[T];
+    if (total > a.max_chunks) total = a.max_chunks;        // a table that overlaps itself: the records hold max_chunks, nothing is written past them
+
+    for (long c = blockIdx.x; c < total; c += gridDim.x) {
+        int lo = 0, hi = T - 1;                            // the tensor of chunk c: the last t with s_first[t] <= c
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if (s_first[mid] <= c) lo = mid; else hi = mid - 1;
+        }
+        const int t = lo;
+        const int chunks = s_first[t + 1] - s_first[t];
+        const long k = c - s_first[t];
+        long b = a.begin[t], m = a.numel[t];
+        if (!(b >= 0 && m > 0 && (b & 3) == 0 && b <= a.n && m <= a.n - b) || k < 0 || k * STAT_CHUNK > m) { b = 0; m = 0; }
+        const long e0 = m ? k * STAT_CHUNK : 0;            // the chunk: elements [e0, e1) of the tensor
+        const long e1 = e0 + STAT_CHUNK < m ? e0 + STAT_CHUNK : m;
+        const long nvec = e1 > e0 ? (e1 - e0) >> 2 : 0;
+        const f32x4_t* g4 = (const f32x4_t*)(a.g + b + e0);
+        const f32x4_t* p4 = WITH_P ? (const f32x4_t*)(a.p + b + e0) : nullptr;
+        StatAcc acc = {0.0, 0.0, 0.0, 0.0};
+        long i = tid;
+        for (; i + (STAT_UNROLL - 1) * OPT_THREADS < nvec; i += STAT_UNROLL * OPT_THREADS) {
+            f32x4_t x[STAT_UNROLL], y[STAT_UNROLL];
+#pragma unroll
+            for (int u = 0; u < STAT_UNROLL; ++u) {
+                x[u] = g4[i + u * OPT_THREADS];
+                if (WITH_P) y[u] = p4[i + u * OPT_THREADS];
+            }
+#pragma unroll
+            for (int u = 0; u < STAT_UNROLL; ++u) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    stat_add_g(acc, x[u][q]);
+                    if (WITH_P) acc.sp += (double)y[u][q] * (double)y[u][q];
+                }
+            }
+        }
+        for (; i < nvec; i += OPT_THREADS) {
+            const f32x4_t x = g4[i];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) stat_add_g(acc, x[q]);
+            if (WITH_P) {
+                const f32x4_t y = p4[i];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) acc.sp += (double)y[q] * (double)y[q];
+            }
+        }
+        if (e1 == m && e1 > e0 && tid < (int)(m & 3)) {    // the tensor's trailing elements, in its last chunk
+            const long j = b + (m & ~3L) + tid;
+            stat_add_g(acc, a.g[j]);
+            if (WITH_P) acc.sp += (double)a.p[j] * (double)a.p[j];
+        }
+        stat_fold(acc, s_fold);
+        if (chunks == 1) {                                 // finished here: no record, no ticket
+            if (tid == 0) { double* o = a.out + 4L * t; o[0] = acc.sg; o[1] = acc.amax; o[2] = acc.nf; o[3] = acc.sp; }
+            continue;
+        }
+        if (tid == 0) {
+            double* r = a.records + 4 * c;
+            handoff::publish(r, acc.sg); handoff::publish(r + 1, acc.amax); handoff::publish(r + 2, acc.nf); handoff::publish(r + 3, acc.sp);
+        }
+        if (!handoff::arrive<true>([&] { return a.tickets + t; }, [&] { return chunks; }, a.fences, a.fences, &s_last)) continue;
+        // the last of this tensor's workgroups: its records in index order
+        const double* r0 = a.records + 4L * s_first[t];
+        StatAcc tot = {0.0, 0.0, 0.0, 0.0};
+        for (int j = tid; j < chunks; j += OPT_THREADS) {
+            tot.sg += handoff::read(r0 + 4L * j);
+            tot.amax = fmax(tot.amax, handoff::read(r0 + 4L * j + 1));
+            tot.nf += handoff::read(r0 + 4L * j + 2);
+            tot.sp += handoff::read(r0 + 4L * j + 3);
+        }
+        stat_fold(tot, s_fold);
+        if (tid == 0) { double* o = a.out + 4L * t; o[0] = tot.sg; o[1] = tot.amax; o[2] = tot.nf; o[3] = tot.sp; }
+    }
+}
+
 // ---- gradient accumulation over micro-batches --------------------------------------------------------------------------------------------
 // dst[i] = dst[i] + src[i] (one fp32 rounding), or with ASSIGN dst[i] = src[i] (a bit copy: dst is not read), in the step kernels' launch
 // shape.  12 B per element without ASSIGN (read, read, write): the plain SGD launch's count and read:write mix.  No atomics, no state.
@@ -448,6 +736,69 @@ int mte_sgd_step_ctl_dev(float* p, const float* g, float* buf, long n, const flo
     if ((momentum > 0.f && !buf) || (nesterov && momentum <= 0.f)) return MTE_ERR_ARG;
     const SgdScalars s = {0.f, 0.f, 0.f, momentum, gscale, weight_decay};
     return sgd_launch<true, true>(p, g, buf, n, hyper, s, nesterov, ctl, stream);
+}
+
+// The SEG form of mte_adamw_step_dev / mte_sgd_step_dev: per-class multipliers of the learning rate and the weight decay.  block_class[b]
+// (DEVICE memory, n / 64 bytes) is the class of elements 64 b .. 64 b + 63 and class_scales (DEVICE memory, 2 * n_classes floats) holds
+// {lr_mult, wd_mult} per class: lr_c = float32(hyper[0] * lr_mult_c), wd_c = float32(weight_decay * wd_mult_c), then the plain step's
+// arithmetic on every block with its class's pair (wd_c == 0: the no-decay arithmetic).  ctl may be null; otherwise it is
+// mte_grad_norm_clip's word with the meaning it has in the _ctl_dev forms.  n % 64 != 0, a null table, n_classes outside 1..16 and the
+// plain forms' argument errors are MTE_ERR_ARG.  A class byte >= n_classes is read as n_classes - 1.
+int mte_adamw_step_seg_dev(float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                           float weight_decay, int decoupled, float gscale, const uint8_t* block_class, const float* class_scales, int n_classes,
+                           const float* ctl, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!p || !g || !m || !v || !hyper || n <= 0 || !(weight_decay >= 0.f)) return MTE_ERR_ARG;
+    if ((n & 63) || !block_class || !class_scales || n_classes < 1 || n_classes > SEG_MAX_CLASSES) return MTE_ERR_ARG;
+    const AdamScalars s = {0.f, 0.f, 0.f, beta1, beta2, eps, gscale, weight_decay};
+    const SegArgs t = {block_class, class_scales, ctl, n_classes};
+    const dim3 grid(opt_grid(n >> 2)), block(OPT_THREADS);
+    if (s.wd == 0.f) hipLaunchKernelGGL((adamw_seg_kernel<WD_NONE>), grid, block, 0, stream, p, g, m, v, n, hyper, s, t);
+    else if (decoupled) hipLaunchKernelGGL((adamw_seg_kernel<WD_DECOUPLED>), grid, block, 0, stream, p, g, m, v, n, hyper, s, t);
+    else hipLaunchKernelGGL((adamw_seg_kernel<WD_L2>), grid, block, 0, stream, p, g, m, v, n, hyper, s, t);
+    return mte_check_launch();
+}
+
+int mte_sgd_step_seg_dev(float* p, const float* g, float* buf, long n, const float* hyper, float momentum, float weight_decay, int nesterov,
+                         float gscale, const uint8_t* block_class, const float* class_scales, int n_classes, const float* ctl,
+                         hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!p || !g || !hyper || n <= 0 || !(momentum >= 0.f) || !(weight_decay >= 0.f)) return MTE_ERR_ARG;
+    if ((momentum > 0.f && !buf) || (nesterov && momentum <= 0.f)) return MTE_ERR_ARG;
+    if ((n & 63) || !block_class || !class_scales || n_classes < 1 || n_classes > SEG_MAX_CLASSES) return MTE_ERR_ARG;
+    const SgdScalars s = {0.f, 0.f, 0.f, momentum, gscale, weight_decay};
+    const SegArgs t = {block_class, class_scales, ctl, n_classes};
+    if (s.mu == 0.f) sgd_seg_launch_wd<MOM_NONE>(p, g, buf, n, hyper, s, t, stream);
+    else if (nesterov) sgd_seg_launch_wd<MOM_NESTEROV>(p, g, buf, n, hyper, s, t, stream);
+    else sgd_seg_launch_wd<MOM_PLAIN>(p, g, buf, n, hyper, s, t, stream);
+    return mte_check_launch();
+}
+
+// Bytes of `work` for mte_tensor_stats over T tensors inside n flat elements (16-byte aligned, zeroed ONCE by the caller): one ticket per
+// tensor, then one record of four fp64 values per chunk.  0 for n <= 0 or T outside 1..4096.
+long mte_tensor_stats_work_bytes(long n, int T) {
+    return (n <= 0 || T < 1 || T > STAT_MAX_T) ? 0 : stat_ticket_bytes(T) + 32L * stat_max_chunks(n, T);
+}
+
+// Per-tensor statistics of the flat gradient g[0..n) and, with p non-null, of the weights p[0..n) (both 16-byte aligned; read-only) in ONE
+// launch: tensor t is elements seg_begin[t] .. seg_begin[t] + seg_numel[t] - 1 (`long` arrays in DEVICE memory; begins are multiples of
+// 64, ranges disjoint and inside [0, n)), out[4 t ..] = {sum g^2, max |g| over the finite elements, count of non-finite elements,
+// sum p^2 (0 without p)} as fp64 in DEVICE memory.  The order of every addition is fixed by the table (see the kernel): bit-equal call
+// to call and under graph replay; the tickets in `work` go back to zero.  A range that leaves [0, n) reads nothing and reports zeros.
+int mte_tensor_stats(const float* g, const float* p, long n, const long* seg_begin, const long* seg_numel, int T, void* work, double* out,
+                     hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!g || !seg_begin || !seg_numel || !work || !out || n <= 0 || T < 1 || T > STAT_MAX_T) return MTE_ERR_ARG;
+    if ((((uintptr_t)g | (uintptr_t)p | (uintptr_t)work) & 15) || stat_max_chunks(n, T) > 0x7fffffffL) return MTE_ERR_ARG;
+    StatArgs a;
+    a.g = g; a.p = p; a.n = n; a.begin = seg_begin; a.numel = seg_numel; a.T = T; a.fences = g_mte_handoff_fences;
+    a.max_chunks = stat_max_chunks(n, T);
+    a.tickets = (unsigned*)work; a.records = (double*)((char*)work + stat_ticket_bytes(T)); a.out = out;
+    const long want = a.max_chunks;
+    const dim3 grid((unsigned)(want > STAT_CAP ? STAT_CAP : want)), block(OPT_THREADS);
+    if (p) hipLaunchKernelGGL(tensor_stats_kernel<true>, grid, block, 0, stream, a);
+    else hipLaunchKernelGGL(tensor_stats_kernel<false>, grid, block, 0, stream, a);
+    return mte_check_launch();
 }
 
 }  // extern "C"

@@ -99,10 +99,13 @@ class ModelWrapper(nn.Module):
         gradient-norm clipping and non-finite step guard of FusedFlatOptimizer; config.arch.accumulate_grad_batches > 1 its gradient
         accumulation over micro-batches; config.model.optimizer.ema_decay > 0 (with ema_warmup) its exponential moving average of the
         weights, which Trainer.validate swaps in when ema_validate is set.  A resumed file's 'state_dict_ema' / 'ema' entries restore
-        the average and its update count; without them the average starts from the loaded weights at count 0."""
+        the average and its update count; without them the average starts from the loaded weights at count 0.
+        config.model.optimizer.tensor_scales (a list of rules {pattern, max_ndim, lr_scale, weight_decay_scale}, see
+        resolve_tensor_scales) gives tensors their own multiples of the group's lr and weight_decay -- the fused SEG steps, still one
+        param group; config.model.optimizer.log_tensor_stats = k > 0 makes the trainer print per-tensor gradient statistics."""
         import torch.distributed as dist
         from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedSGD, broadcast_parameters,
-                                              reference_parameter_names)
+                                              reference_parameter_names, resolve_tensor_scales)
         opt_cfg = self.config.model.optimizer
         built = {'Adam': FusedAdam, 'AdamW': FusedAdam, 'SGD': FusedSGD}
         if opt_cfg.name not in built:
@@ -129,12 +132,21 @@ class ModelWrapper(nn.Module):
         accumulate = getattr(self.trainer, 'accumulate_grad_batches', None)
         if accumulate is None:
             accumulate = self.config.arch.accumulate_grad_batches or 1
+        # model.optimizer.tensor_scales: rules -> one (lr_scale, weight_decay_scale) per trained tensor by its reference name and shape
+        # (resolve_tensor_scales); no rule, or rules that leave every tensor at (1, 1), build the optimizer that was always built
+        local = dict(self.depth_net.named_parameters())
+        rules = opt_cfg.get('tensor_scales') or []
+        if rules:
+            name_of = {id(p): n for n, p in local.items()}
+            names = [name_of[id(p)] for p in flat.natural_params]
+            kwargs['tensor_scales'] = resolve_tensor_scales(names, [tuple(p.shape) for p in flat.natural_params], rules)
         optimizer = built[opt_cfg.name](flat, reducer=reducer, name='Depth', clip_grad_norm=float(opt_cfg.clip_grad_norm or 0.0),
                                         skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), accumulate_grad_batches=accumulate,
                                         ema_decay=float(opt_cfg.get('ema_decay') or 0.0),
                                         ema_warmup=True if opt_cfg.get('ema_warmup') is None else bool(opt_cfg.get('ema_warmup')), **kwargs)
         self.ema_validate = True if opt_cfg.get('ema_validate') is None else bool(opt_cfg.get('ema_validate'))
-        optimizer.set_index_space(reference_parameter_names(self.depth_net), dict(self.depth_net.named_parameters()))
+        self.log_tensor_stats = int(opt_cfg.get('log_tensor_stats') or 0)
+        optimizer.set_index_space(reference_parameter_names(self.depth_net), local)
         sched = getattr(torch.optim.lr_scheduler, self.config.model.scheduler.name)
         scheduler = sched(optimizer, **filter_args(sched, self.config.model.scheduler))
         if self.resume:

@@ -71,6 +71,34 @@ class FlatParameters:
             self.ema = self.flat.clone()
         return self.ema
 
+    def segments(self, device=None):
+        """The tensor layout of the flat buffers: one (begin, numel, slot) per tensor in FLAT order -- begin a multiple of ``align``,
+        numel the tensor's true element count (the padding behind it is not part of it), slot the tensor's position in
+        ``natural_params``.  With ``device``: (begins, numels) as two int64 tensors there instead, made on this call and not kept."""
+        slot = {id(p): i for i, p in enumerate(self.natural_params)}
+        segs = [(o, p.numel(), slot[id(p)]) for p, o in zip(self.params, self.offsets)]
+        if device is None:
+            return segs
+        return (torch.tensor([s[0] for s in segs], dtype=torch.int64, device=device),
+                torch.tensor([s[1] for s in segs], dtype=torch.int64, device=device))
+
+    def block_classes(self, class_of_tensor, device=None):
+        """The ``total / 64`` byte map of the SEG optimizer steps: entry b is the class of elements 64 b .. 64 b + 63.
+        ``class_of_tensor``: one class id (0..255) per tensor in ``natural_params`` order.  Every tensor starts on a 64-element boundary,
+        so a block belongs to one tensor; the padding blocks behind a tensor carry its class.  A uint8 tensor on the host, or on
+        ``device`` when given (made on this call, not kept)."""
+        if self.total % 64 or any(o % 64 for o in self.offsets):
+            raise ValueError("block_classes needs a layout aligned to 64 elements")
+        if len(class_of_tensor) != len(self.natural_params):
+            raise ValueError("block_classes takes one class per tensor: {} for {} tensors".format(len(class_of_tensor), len(self.natural_params)))
+        if any(int(c) != c or not 0 <= int(c) <= 255 for c in class_of_tensor):
+            raise ValueError("class ids are integers in 0..255")
+        out = torch.empty(self.total // 64, dtype=torch.uint8)
+        ends = self.offsets[1:] + [self.total]
+        for (o, _, slot), e in zip(self.segments(), ends):
+            out[o // 64:e // 64] = int(class_of_tensor[slot])
+        return out if device is None else out.to(device)
+
     def zero_grad(self):
         if self.grad.is_cuda:
             from .. import kernels as K
@@ -235,6 +263,64 @@ def ema_decay_pair(t, decay, warmup=True):
     return d32, f32(1.0 - d32)
 
 
+MAX_SCALE_CLASSES = 16                                       # the SEG kernels' class table (csrc/optim.hip: SEG_MAX_CLASSES)
+
+
+def tensor_scale_classes(pairs):
+    """[(lr_mult, wd_mult)] per tensor -> (classes, class_of_tensor): the distinct pairs in order of first appearance and every tensor's
+    index into them.  Multipliers must be finite and >= 0; more than MAX_SCALE_CLASSES distinct pairs is a ValueError."""
+    import math
+    classes, index, class_of = [], {}, []
+    for i, pair in enumerate(pairs):
+        lm, wm = float(pair[0]), float(pair[1])
+        for what, x in (('lr_scale', lm), ('weight_decay_scale', wm)):
+            if not (math.isfinite(x) and x >= 0.0):
+                raise ValueError("Invalid {} {} for tensor {}: multipliers are finite and >= 0".format(what, x, i))
+        if (lm, wm) not in index:
+            index[(lm, wm)] = len(classes)
+            classes.append((lm, wm))
+        class_of.append(index[(lm, wm)])
+    if len(classes) > MAX_SCALE_CLASSES:
+        raise ValueError("tensor_scales hold {} distinct (lr_scale, weight_decay_scale) pairs; the fused steps take at most {}".format(
+            len(classes), MAX_SCALE_CLASSES))
+    return classes, class_of
+
+
+def resolve_tensor_scales(names, shapes, rules):
+    """model.optimizer.tensor_scales -> one (lr_scale, weight_decay_scale) per tensor.
+
+    names / shapes: the trained tensors' reference names and shapes, in one order.  rules: a list of {pattern, max_ndim, lr_scale,
+    weight_decay_scale}: a rule MATCHES a tensor when re.search(pattern, name) finds something (no pattern: every name) and, with
+    max_ndim, the tensor has at most that many dimensions.  For each tensor and each of the two attributes on its own, the first
+    matching rule that names the attribute gives its value; a tensor that no such rule reaches gets 1.  A rule that matches no tensor
+    at all is a ValueError that shows its pattern (a typo must not pass silently), as are an unknown key, a rule that names neither
+    attribute, a negative or non-finite multiplier and more than MAX_SCALE_CLASSES distinct pairs."""
+    import re
+    keys = ('lr_scale', 'weight_decay_scale')
+    out = [[None, None] for _ in names]
+    for rule in (rules or ()):
+        rule = dict(rule)
+        unknown = set(rule) - {'pattern', 'max_ndim'} - set(keys)
+        if unknown or not any(rule.get(k) is not None for k in keys):
+            raise ValueError("tensor_scales rule {}: keys are pattern, max_ndim, lr_scale, weight_decay_scale, and a rule names at least "
+                             "one of the two scales".format(rule))
+        pattern, max_ndim = rule.get('pattern'), rule.get('max_ndim')
+        rx = re.compile(pattern) if pattern is not None else None
+        hit = False
+        for i, (name, shape) in enumerate(zip(names, shapes)):
+            if (rx is not None and not rx.search(name)) or (max_ndim is not None and len(shape) > int(max_ndim)):
+                continue
+            hit = True
+            for j, k in enumerate(keys):
+                if rule.get(k) is not None and out[i][j] is None:
+                    out[i][j] = float(rule[k])
+        if not hit:
+            raise ValueError("tensor_scales rule with pattern {!r} (max_ndim {}) matches no trained tensor".format(pattern, max_ndim))
+    pairs = [(1.0 if a is None else a, 1.0 if b is None else b) for a, b in out]
+    tensor_scale_classes(pairs)                              # the multipliers' and the class limit's ValueErrors
+    return pairs
+
+
 class FusedFlatOptimizer(torch.optim.Optimizer):
     """What the fused optimizers share: ONE HBM-bound kernel over the flat buffers per step, with everything around it -- the reducer's
     wait and its gradient scale, the gradient sink, the side stream, the weight-pack epoch and prefetch, the device error poll, the three
@@ -283,16 +369,42 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     was skipped: ``ema_updates`` advances anyway, so the warm-up schedule counts skipped steps just as Adam's bias correction does.
     ``ema_weights()`` swaps weights and average for validation; ``ema_state()`` / ``load_ema()`` / ``ema_named()`` carry the average to
     and from checkpoints.  None of it is part of ``state_dict()``, which stays torch's layout.  With ema_decay = 0 -- the default --
-    there is no buffer, no scalar pair and no launch."""
+    there is no buffer, no scalar pair and no launch.
 
-    HAS_STEP = False                                         # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
+    Per-tensor multipliers (``tensor_scales``: one (lr_mult, wd_mult) per parameter, in the order the parameters were handed to
+    FlatParameters).  ``param_groups`` stays ONE group -- the checkpoint layout is torch's, numbered in the reference's index space --
+    and the base ``lr`` stays in it, so a scheduler's change reaches every tensor.  Distinct pairs become classes (at most 16);
+    ``seg_block_class`` (one byte per aligned 64-element block of the flat buffers) and ``seg_class_scales`` ({lr_mult, wd_mult} per
+    class) are uploaded once, and ``step()`` launches the SEG entry point (mte_adamw_step_seg_dev / mte_sgd_step_seg_dev; with ``ctl``
+    when clipping or the guard is on, behind the same global norm launch), also for plain Adam without weight decay.  Per class
+    lr_c = float32(lr * lr_mult) and wd_c = float32(weight_decay * wd_mult); wd_c = 0 takes the no-decay arithmetic.  The launch is
+    static: it replays from a captured graph.  Multipliers and tables are configuration, not ``state_dict()``.  ``None``, or every
+    pair (1, 1), is OFF: no table, no attribute, and ``_launch`` / ``_launch_ctl`` are the launches described above.
+
+    ``tensor_stats()``: per-tensor gradient norm, largest finite |g|, count of non-finite gradient elements and weight norm in ONE
+    read-only launch (mte_tensor_stats) and one host read, whether or not ``tensor_scales`` is set; never launched by ``step()``."""
+
+    HAS_STEP = False                                        # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
     LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
     LOAD_KEYS = ('lr', 'initial_lr')
 
     def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1,
-                 ema_decay=0.0, ema_warmup=True):
+                 ema_decay=0.0, ema_warmup=True, tensor_scales=None):
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("Invalid ema_decay value: {} (in [0, 1); 0 = off)".format(ema_decay))
+        if tensor_scales is not None:
+            tensor_scales = [(float(a), float(b)) for a, b in tensor_scales]
+            if len(tensor_scales) != len(flat.natural_params):
+                raise ValueError("tensor_scales holds {} pairs for {} trained tensors".format(len(tensor_scales), len(flat.natural_params)))
+            classes, class_of = tensor_scale_classes(tensor_scales)
+            if classes != [(1.0, 1.0)]:
+                # only then: the default optimizer has no tables, none of these attributes and no SEG launch
+                dev = flat.flat.device
+                self.tensor_scales = tensor_scales
+                self.seg_classes = classes
+                self.seg_block_class = flat.block_classes(class_of, device=dev)
+                self.seg_class_scales = torch.tensor([x for pair in classes for x in pair], dtype=torch.float32, device=dev)
+        self._last_gscale = 1.0                               # the last step's gradient scale, for tensor_stats()
         if not float(clip_grad_norm) >= 0.0:
             raise ValueError("Invalid clip_grad_norm value: {} (0 = off)".format(clip_grad_norm))
         if int(accumulate_grad_batches) != accumulate_grad_batches or int(accumulate_grad_batches) < 1:
@@ -329,6 +441,41 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         device), for tests and logging"""
         c = self.ctl.tolist()
         return {'grad_norm': c[2], 'clip_coef': c[0], 'skipped': bool(c[1]), 'skipped_steps': int(c[3])}
+
+    @torch.no_grad()
+    def tensor_stats(self, with_weights=True):
+        """One dict per trained tensor, in the order of the reference's numbering (set_index_space; positional names without it):
+        {'name', 'numel', 'grad_norm' (|gscale| * sqrt(sum g^2) with the last step's gscale), 'grad_amax' (largest finite |g|, unscaled),
+        'nonfinite' (inf / NaN elements of the gradient), 'weight_norm' (0.0 without ``with_weights``), 'lr_scale',
+        'weight_decay_scale', 'grad_sq_sum' (the unscaled fp64 sum g^2)}.  ONE read-only launch over ``flat.grad`` as it stands (mte_tensor_stats; fp64 sums in an order the layout
+        fixes) and ONE host read.  Call it after step() and before zero_grad(): the steps never rescale the gradient buffer, so it
+        still holds the step's gradient (with accumulation, the group's sum)."""
+        import math
+        from .. import kernels as K
+        flat = self.flatp
+        K._require_gpu(flat.grad)
+        segs = flat.segments()
+        if getattr(self, '_stats_tables', None) is None:
+            dev = flat.grad.device
+            work = torch.zeros((int(K.lib.mte_tensor_stats_work_bytes(flat.total, len(segs))) + 7) // 8, dtype=torch.float64, device=dev)
+            self._stats_tables = flat.segments(device=dev) + (work, torch.zeros(4 * len(segs), dtype=torch.float64, device=dev))
+        begins, numels, work, out = self._stats_tables
+        K.lib.mte_tensor_stats(flat.grad.data_ptr(), flat.flat.data_ptr() if with_weights else None, flat.total, begins.data_ptr(),
+                               numels.data_ptr(), len(segs), work.data_ptr(), out.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        rows = out.view(-1, 4).tolist()                       # the one host read
+        row_of = {id(p): r for p, r in zip(flat.params, rows)}
+        slot_of = {id(p): i for i, p in enumerate(flat.natural_params)}
+        scales = getattr(self, 'tensor_scales', None)
+        res = []
+        for pos, (name, p, _) in enumerate(self._space()):
+            if p is None:
+                continue
+            sg, amax, nf, sp = row_of[id(p)]
+            lm, wm = scales[slot_of[id(p)]] if scales is not None else (1.0, 1.0)
+            res.append({'name': name if name is not None else str(pos), 'numel': p.numel(), 'grad_norm': abs(self._last_gscale) * math.sqrt(sg),
+                        'grad_amax': amax, 'nonfinite': int(nf), 'weight_norm': math.sqrt(sp), 'lr_scale': lm, 'weight_decay_scale': wm,
+                        'grad_sq_sum': sg})                   # the unscaled fp64 sum of squares as the launch left it
+        return res
 
     def _norm_clip(self, K, gscale, stream):
         """ctl <- the clip coefficient / skip flag of the gradient as it stands (reduced and complete)"""
@@ -402,17 +549,24 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             if not torch.cuda.is_current_stream_capturing():
                 self.advance()
             stream = torch.cuda.current_stream().cuda_stream
-            if getattr(self, 'ctl', None) is None:
+            self._last_gscale = float(gscale)
+            ctl = getattr(self, 'ctl', None)
+            if ctl is not None:
+                self._norm_clip(K, float(gscale), stream)
+            if getattr(self, 'seg_block_class', None) is not None:
+                self._launch_seg(K, g, float(gscale), (self.seg_block_class.data_ptr(), self.seg_class_scales.data_ptr(), len(self.seg_classes),
+                                                       None if ctl is None else ctl.data_ptr()), stream)
+            elif ctl is None:
                 self._launch(K, g, float(gscale), stream)
             else:
-                self._norm_clip(K, float(gscale), stream)
                 self._launch_ctl(K, g, float(gscale), stream)
             if self.ema_decay > 0.0:                         # the average follows the weights the step just wrote (or, skipped, left alone)
                 K.ema_update_flat(self.flatp.ema, self.flatp.flat, self.ema_scal, getattr(self, 'ctl', None), stream)
             K.bump_weights_epoch()
         else:
             self.steps += 1
-            self._host_step(K, g, gscale)                    # no CPU form: raises MteError on host buffers
+            self._last_gscale = float(gscale)
+            self._host_step(K, g, gscale)                  # no CPU form: raises MteError on host buffers
         if self.flatp.grad.is_cuda:
             K.prefetch_weight_packs()                       # next step's kernel-ready weight packs, off the critical path
             if not torch.cuda.is_current_stream_capturing():
@@ -636,14 +790,14 @@ class FusedAdam(FusedFlatOptimizer):
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
                  decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0,
-                 ema_warmup=True):
+                 ema_warmup=True, tensor_scales=None):
         if not 0.0 <= float(weight_decay):
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
         super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                     capturable=False, differentiable=False, fused=None,
                                     decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name,
                          clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
 
@@ -664,6 +818,11 @@ class FusedAdam(FusedFlatOptimizer):
         """clipped / guarded: weight_decay = 0 is adamw_kernel's WD_NONE instance, the Adam step operation for operation"""
         K.lib.mte_adamw_step_ctl_dev(*self._bufs(g), float(g['weight_decay']), int(bool(g['decoupled_weight_decay'])), gscale,
                                      self.ctl.data_ptr(), stream)
+
+    def _launch_seg(self, K, g, gscale, tables, stream):
+        """per-tensor multipliers: tables = (block classes, class scales, classes, ctl or None); also without a weight decay, where the
+        learning-rate multipliers still act"""
+        K.lib.mte_adamw_step_seg_dev(*self._bufs(g), float(g['weight_decay']), int(bool(g['decoupled_weight_decay'])), gscale, *tables, stream)
 
     def _launch(self, K, g, gscale, stream):
         wd = float(g['weight_decay'])
@@ -693,7 +852,7 @@ class FusedSGD(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
 
     def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth',
-                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True):
+                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True, tensor_scales=None):
         if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
             raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
         if nesterov and (momentum <= 0 or dampening != 0):
@@ -701,7 +860,7 @@ class FusedSGD(FusedFlatOptimizer):
         super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                     maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name,
                          clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales)
         self.momentum_buffer = None
         self.state_buffers()
 
@@ -727,6 +886,12 @@ class FusedSGD(FusedFlatOptimizer):
     def _launch(self, K, g, gscale, stream):
         K.lib.mte_sgd_step_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),
                                self.hyper.data_ptr(), float(g['momentum']), float(g['weight_decay']), int(bool(g['nesterov'])), gscale, stream)
+
+    def _launch_seg(self, K, g, gscale, tables, stream):
+        """per-tensor multipliers: tables = (block classes, class scales, classes, ctl or None)"""
+        K.lib.mte_sgd_step_seg_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),
+                                   self.hyper.data_ptr(), float(g['momentum']), float(g['weight_decay']), int(bool(g['nesterov'])), gscale,
+                                   *tables, stream)
 
     def _launch_ctl(self, K, g, gscale, stream):
         K.lib.mte_sgd_step_ctl_dev(self.flatp.flat.data_ptr(), self.flatp.grad.data_ptr(), self._buf_ptr(), self.flatp.flat.numel(),

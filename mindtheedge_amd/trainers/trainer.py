@@ -54,6 +54,18 @@ def _with_group_end(dataloader, k):
             yield batch, last
 
 
+def tensor_stats_lines(stats, k):
+    """The log lines of model.optimizer.log_tensor_stats = k from FusedFlatOptimizer.tensor_stats(): the k tensors with the largest
+    gradient norm (non-finite norms first), then every tensor whose gradient holds an inf or a NaN, by name"""
+    def key(s):
+        return (0, 0.0) if s['grad_norm'] != s['grad_norm'] or s['grad_norm'] == float('inf') else (1, -s['grad_norm'])
+    lines = ['  grad top {} | {} | norm {:.4g} | amax {:.4g} | weight norm {:.4g} | lr x{:g} | wd x{:g}'.format(
+        i + 1, s['name'], s['grad_norm'], s['grad_amax'], s['weight_norm'], s['lr_scale'], s['weight_decay_scale'])
+        for i, s in enumerate(sorted(stats, key=key)[:int(k)])]
+    lines += ['  grad non-finite | {} | {} of {} elements'.format(s['name'], s['nonfinite'], s['numel']) for s in stats if s['nonfinite'] > 0]
+    return lines
+
+
 class Trainer:
     def __init__(self, min_epochs=0, max_epochs=50, validate_first=False, checkpoint=None, log_every=50, accumulate_grad_batches=None,
                  **kwargs):
@@ -179,6 +191,11 @@ class Trainer:
                 if ctl is not None:
                     line += ' | Grad norm {:.4f} | Skipped {}'.format(last[3], int(last[4]))
                 print(line, flush=True)
+                if getattr(module, 'log_tensor_stats', 0) > 0 and hasattr(optimizer, 'tensor_stats'):
+                    # model.optimizer.log_tensor_stats: one more read-only launch and host read per log line; the gradient buffer still
+                    # holds this batch's gradient (zero_grad comes with the next batch)
+                    for extra in tensor_stats_lines(optimizer.tensor_stats(), module.log_tensor_stats):
+                        print(extra, flush=True)
         if n:
             last = read()
         out = {'steps': n, 'avg_loss': last[0] if last else None, 'avg_supervised': last[1] if last else None,

@@ -32,8 +32,12 @@ _DEFAULTS = {
         # beside `name`, not under `depth`, so filter_args never hands them to torch.optim; both off = the step as it always was.
         # ema_decay (0 = off): FusedFlatOptimizer keeps an exponential moving average of the trained tensors with that decay (ema_warmup: the
         # decay of the t-th update is min(ema_decay, (1 + t) / (10 + t))); ema_validate: validation, and with it save_top_k, runs on the average.
+        # tensor_scales ([] = off): rules {pattern: regex on the reference parameter name, max_ndim, lr_scale, weight_decay_scale} that give tensors
+        # multiples of the group's lr / weight_decay (first matching rule per attribute; trainers/data_parallel.py::resolve_tensor_scales).
+        # log_tensor_stats (0 = off): k > 0 prints, after each training log line, the k tensors with the largest gradient norm and every tensor
+        # whose gradient holds an inf or a NaN.
         'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}, 'clip_grad_norm': 0.0, 'skip_nonfinite_steps': False,
-                      'ema_decay': 0.0, 'ema_warmup': True, 'ema_validate': True},
+                      'ema_decay': 0.0, 'ema_warmup': True, 'ema_validate': True, 'tensor_scales': [], 'log_tensor_stats': 0},
         'scheduler': {'name': 'StepLR', 'step_size': 10, 'gamma': 0.5},
         'params': {'crop': '', 'min_depth': 0.0, 'max_depth': 80.0, 'scale_output': 'resize'},     # default_config.py:84-87
         'loss': {'supervised_method': 'sparse-l1', 'supervised_num_scales': 4, 'supervised_loss_weight': 0.9,
