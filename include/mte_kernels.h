@@ -508,6 +508,39 @@ int mte_sgd_step_seg_dev(float* p, const float* g, float* buf, long n, const flo
 long mte_tensor_stats_work_bytes(long n, int T);
 int mte_tensor_stats(const float* g, const float* p, long n, const long* seg_begin, const long* seg_numel, int T, void* work, double* out,
                      mte_stream_t stream);
+/* ---- LAMB (csrc/optim.hip): the decoupled AdamW step whose per-tensor delta is rescaled by a trust ratio, as TWO launches with no
+ * scratch buffer.  The tensor table is mte_tensor_stats' (seg_begin / seg_numel: `long` arrays of T entries in DEVICE memory, begins
+ * multiples of 64, ranges disjoint, 1 <= T <= 4096) plus tensor_table (DEVICE memory, 3 * T floats): {lr_mult, wd_mult, adapt} per tensor.
+ * hyper = {lr, 1 - beta1^t, sqrt(1 - beta2^t)} in DEVICE memory, as mte_adamw_step_dev.  Per tensor t, in fp32 with contraction off:
+ *     lr_t = float32(hyper[0] * lr_mult)    wd_t = float32(weight_decay * wd_mult)    lrwd = lr_t * wd_t
+ *     g'   = g * gs                         (gs = gscale, or float32(gscale * ctl[0]) with a ctl)
+ *     m    = b1 * m + (1 - b1) * g'         v = b2 * v + (1 - b2) * g' * g'
+ *     den  = sqrtf(v) / hyper[2] + eps
+ *     d    = lrwd * p + (lr_t / hyper[1]) * (m / den)          (wd_t == 0: the no-decay form, d = (lr_t / hyper[1]) * (m / den))
+ *     S_p  = sum (double)p^2    S_d = sum (double)d^2          over the tensor's numel elements; the padding behind them is never read
+ *     r_t  = adapt != 0 && S_p > 0 && S_d > 0 ? lr_t * sqrt(S_p) / sqrt(S_d) (fp64) : 1;   max_trust > 0: r_t = min(r_t, max_trust)
+ *     q_t  = float32(r_t)                   p = p - q_t * d
+ *   d = lr_t * u with u the LAMB paper's update, so q_t = ||p|| / ||u|| is its trust ratio.  With q_t = 1 the step is
+ *   mte_adamw_step_dev (decoupled) bit for bit.  Non-finite sums get no special case: a NaN gives r_t = 1 and reaches p through d.
+ * mte_lamb_moments (24 B per parameter): reads p, g, m, v, writes m, v, and leaves trust[t] = q_t (T floats) and sums[2 t ..] =
+ *   {S_p, S_d} (2 * T doubles), both DEVICE memory.  The sums are fp64 in an order the table alone fixes (mte_tensor_stats' chunks, one
+ *   record per chunk, a ticket per tensor; no floating-point atomics): bit-equal call to call and under graph replay.
+ *   `work`: mte_lamb_work_bytes(n, T) bytes (0 for n <= 0 or T outside 1..4096), 16-byte aligned, zeroed ONCE by the caller; its
+ *   tickets return to zero.
+ * mte_lamb_apply (16 B per parameter): reads p, m, v and trust, forms d again from the stored m and v (the same operations on the same
+ *   inputs: the same bits) and writes p.  It takes the hyper, eps, weight_decay, table and ctl of the mte_lamb_moments launch before it.
+ * ctl may be null; otherwise it is mte_grad_norm_clip's word, and with ctl[1] != 0 BOTH launches return before their first load: p, m,
+ *   v, trust, sums and work keep their bits.
+ * MTE_ERR_ARG: a null pointer (except ctl); p, g, m, v or work not 16-byte aligned (sums: 8-byte); n <= 0; T outside 1..4096; a negative
+ *   or NaN weight_decay or max_trust.  A table range that leaves [0, n) reads and writes nothing in the flat buffers for that tensor (its
+ *   trust is 1 and its sums are 0), as in mte_tensor_stats. */
+long mte_lamb_work_bytes(long n, int T);
+int mte_lamb_moments(const float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                     float weight_decay, float gscale, float max_trust, const long* seg_begin, const long* seg_numel,
+                     const float* tensor_table, int T, void* work, float* trust, double* sums, const float* ctl, mte_stream_t stream);
+int mte_lamb_apply(float* p, const float* m, const float* v, long n, const float* hyper, float eps, float weight_decay,
+                   const long* seg_begin, const long* seg_numel, const float* tensor_table, int T, const float* trust,
+                   const float* ctl, mte_stream_t stream);
 
 /* ---- validation depth metrics: fp32 [B,1,H,W] maps, no host synchronisation
  * mte_post_process_inv_depth = post_process_inv_depth (utils/depth.py:230-256); method 0 'mean', 1 'max', 2 'min'

@@ -28,6 +28,8 @@
 // FusedFlatOptimizer(tensor_scales=...).  Kernels of their own: adamw_kernel / sgd_kernel and their instances are what they were.
 // Per-tensor gradient statistics: mte_tensor_stats, one read-only launch over the gradient (and the weights) with the tensor table in
 // device memory, fp64 sums in an order fixed by that table.
+// LAMB: mte_lamb_moments + mte_lamb_apply (24 + 16 B per parameter), the decoupled AdamW arithmetic with the per-tensor delta rescaled by
+// ||p|| / ||update|| -- FusedLAMB.  The pair walks the statistics launch's tensor table and chunks; the step kernels above are untouched.
 #include "common.hpp"
 #include "handoff.hpp"
 #include <cstdint>
@@ -60,15 +62,27 @@ inline StepScalars<S, CTL> step_scalars(const S& s, const float* ctl) {
 //               decay is held relative to lr * wd * p, not to p)
 struct AdamScalars { float lr, bc1, bc2s, b1, b2, eps, gscale, wd; };
 
+// The element update in its two halves -- the moments, then the delta that leaves p -- so that the LAMB launches (below), which need the
+// delta before p moves, run these very operations: adam_elem is the two in a row, operation for operation what it always was.
 template <int WD>
-__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s, float lrwd) {
+__device__ __forceinline__ void adam_moments(float p, float g, float& m, float& v, const AdamScalars& s) {
     float gk = g * s.gscale;
     if (WD == WD_L2) gk = gk + s.wd * p;
     m = s.b1 * m + (1.f - s.b1) * gk;
     v = s.b2 * v + (1.f - s.b2) * gk * gk;
+}
+
+template <int WD>
+__device__ __forceinline__ float adam_delta(float p, float m, float v, const AdamScalars& s, float lrwd) {
     const float denom = sqrtf(v) / s.bc2s + s.eps;
-    if (WD == WD_DECOUPLED) p -= lrwd * p + (s.lr / s.bc1) * (m / denom);
-    else p -= (s.lr / s.bc1) * (m / denom);
+    if (WD == WD_DECOUPLED) return lrwd * p + (s.lr / s.bc1) * (m / denom);
+    return (s.lr / s.bc1) * (m / denom);
+}
+
+template <int WD>
+__device__ __forceinline__ void adam_elem(float& p, float g, float& m, float& v, const AdamScalars& s, float lrwd) {
+    adam_moments<WD>(p, g, m, v, s);
+    p -= adam_delta<WD>(p, m, v, s, lrwd);
 }
 
 template <int WD, bool DEV, bool CTL>
@@ -414,25 +428,24 @@ __device__ __forceinline__ void stat_fold(StatAcc& a, double (*sh)[4]) {
     __syncthreads();                                       // sh may be written again
 }
 
-template <bool WITH_P>
-__global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(StatArgs a) {
-    __shared__ int s_first[STAT_MAX_T + 1];                // s_first[t]: global index of tensor t's first chunk; s_first[T]: all chunks
-    __shared__ int s_part[OPT_THREADS];
-    __shared__ double s_fold[OPT_THREADS / 64][4];
-    __shared__ int s_last;
-    const int tid = threadIdx.x, T = a.T;
-    constexpr int PER = STAT_MAX_T / OPT_THREADS;          // consecutive tensors per thread in the scan
+// The chunk walk of the per-tensor kernels (tensor_stats_kernel here, the LAMB pair below): ONE statement of how the tensor table is cut
+// into chunks, so that every kernel that walks it gives a chunk the same elements and the same global index.
+// A range that leaves [0, n) counts as empty: nothing outside the buffers is touched.
+__device__ __forceinline__ bool chunk_range_ok(long b, long m, long n) { return b >= 0 && m > 0 && (b & 3) == 0 && b <= n && m <= n - b; }
 
-    // chunk counts and their running sum.  A tensor whose range leaves [0, n) counts as empty: nothing outside the buffers is read.
+// Every thread of the workgroup calls it.  s_first[t] <- the global index of tensor t's first chunk (the running sum of the chunk counts,
+// an empty tensor counting one empty chunk), s_first[T] <- all chunks, which it returns.  s_first: STAT_MAX_T + 1 ints, s_part: 256 ints.
+__device__ __forceinline__ long chunk_table(const long* begin, const long* numel, int T, long n, int* s_first, int* s_part) {
+    const int tid = threadIdx.x;
+    constexpr int PER = STAT_MAX_T / OPT_THREADS;          // consecutive tensors per thread in the scan
     int cnt[PER], mine = 0;
 #pragma unroll
     for (int k = 0; k < PER; ++k) {
         const int t = tid * PER + k;
         int c = 0;
         if (t < T) {
-            const long b = a.begin[t], m = a.numel[t];
-            const bool ok = b >= 0 && m > 0 && (b & 3) == 0 && b <= a.n && m <= a.n - b;
-            c = ok ? (int)((m + STAT_CHUNK - 1) / STAT_CHUNK) : 1;
+            const long b = begin[t], m = numel[t];
+            c = chunk_range_ok(b, m, n) ? (int)((m + STAT_CHUNK - 1) / STAT_CHUNK) : 1;
         }
         cnt[k] = c;
         mine += c;
@@ -454,23 +467,46 @@ __global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(StatArgs a) {
     }
     if (tid == OPT_THREADS - 1) s_first[STAT_MAX_T] = run; // T = STAT_MAX_T: no thread owns index T
     __syncthreads();
-    long total = s_first[T];
+    return s_first[T];
+}
+
+// Chunk c of the table: tensor t (the last one with s_first[t] <= c) of `chunks` chunks, at elements [b + e0, b + e1) of the flat buffers
+// -- nvec whole vectors, and in the tensor's last chunk (e1 == m) its m & 3 trailing elements.  An empty chunk has b = m = e0 = e1 = 0.
+struct Chunk { int t, chunks; long b, m, e0, e1, nvec; };
+
+__device__ __forceinline__ Chunk chunk_at(long c, const int* s_first, const long* begin, const long* numel, int T, long n) {
+    int lo = 0, hi = T - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (s_first[mid] <= c) lo = mid; else hi = mid - 1;
+    }
+    Chunk ch;
+    ch.t = lo;
+    ch.chunks = s_first[lo + 1] - s_first[lo];
+    const long k = c - s_first[lo];
+    ch.b = begin[lo]; ch.m = numel[lo];
+    if (!chunk_range_ok(ch.b, ch.m, n) || k < 0 || k * STAT_CHUNK > ch.m) { ch.b = 0; ch.m = 0; }
+    ch.e0 = ch.m ? k * STAT_CHUNK : 0;
+    ch.e1 = ch.e0 + STAT_CHUNK < ch.m ? ch.e0 + STAT_CHUNK : ch.m;
+    ch.nvec = ch.e1 > ch.e0 ? (ch.e1 - ch.e0) >> 2 : 0;
+    return ch;
+}
+
+template <bool WITH_P>
+__global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(StatArgs a) {
+    __shared__ int s_first[STAT_MAX_T + 1];                // s_first[t]: global index of tensor t's first chunk; s_first[T]: all chunks
+    __shared__ int s_part[OPT_THREADS];
+    __shared__ double s_fold[OPT_THREADS / 64][4];
+    __shared__ int s_last;
+    const int tid = threadIdx.x, T = a.T;
+
+    long total = chunk_table(a.begin, a.numel, T, a.n, s_first, s_part);
     if (total > a.max_chunks) total = a.max_chunks;        // a table that overlaps itself: the records hold max_chunks, nothing is written past them
 
     for (long c = blockIdx.x; c < total; c += gridDim.x) {
-        int lo = 0, hi = T - 1;                            // the tensor of chunk c: the last t with s_first[t] <= c
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (s_first[mid] <= c) lo = mid; else hi = mid - 1;
-        }
-        const int t = lo;
-        const int chunks = s_first[t + 1] - s_first[t];
-        const long k = c - s_first[t];
-        long b = a.begin[t], m = a.numel[t];
-        if (!(b >= 0 && m > 0 && (b & 3) == 0 && b <= a.n && m <= a.n - b) || k < 0 || k * STAT_CHUNK > m) { b = 0; m = 0; }
-        const long e0 = m ? k * STAT_CHUNK : 0;            // the chunk: elements [e0, e1) of the tensor
-        const long e1 = e0 + STAT_CHUNK < m ? e0 + STAT_CHUNK : m;
-        const long nvec = e1 > e0 ? (e1 - e0) >> 2 : 0;
+        const Chunk ch = chunk_at(c, s_first, a.begin, a.numel, T, a.n);
+        const int t = ch.t, chunks = ch.chunks;
+        const long b = ch.b, m = ch.m, e0 = ch.e0, e1 = ch.e1, nvec = ch.nvec;
         const f32x4_t* g4 = (const f32x4_t*)(a.g + b + e0);
         const f32x4_t* p4 = WITH_P ? (const f32x4_t*)(a.p + b + e0) : nullptr;
         StatAcc acc = {0.0, 0.0, 0.0, 0.0};
@@ -527,6 +563,234 @@ __global__ __launch_bounds__(OPT_THREADS) void tensor_stats_kernel(StatArgs a) {
         }
         stat_fold(tot, s_fold);
         if (tid == 0) { double* o = a.out + 4L * t; o[0] = tot.sg; o[1] = tot.amax; o[2] = tot.nf; o[3] = tot.sp; }
+    }
+}
+
+// ---- LAMB: AdamW whose per-tensor delta is rescaled by a trust ratio, as two launches ----------------------------------------------------------
+// (You et al., "Large Batch Optimization for Deep Learning").  Per element the arithmetic is the decoupled AdamW step's -- adam_moments,
+// then adam_delta, on the tensor's own lr_t = float32(hyper[0] * lr_mult) and wd_t = float32(weight_decay * wd_mult), lrwd = lr_t * wd_t,
+// wd_t == 0 taking the no-decay form -- and per tensor the delta d is rescaled before it leaves p:
+//     S_p = sum (double)p^2,  S_d = sum (double)d^2   over the tensor's numel elements (the padding behind them is never read)
+//     r_t = adapt && S_p > 0 && S_d > 0 ? lr_t * sqrt(S_p) / sqrt(S_d) (fp64) : 1;   max_trust > 0: r_t = min(r_t, max_trust)
+//     q_t = float32(r_t);   p = p - q_t * d
+// d = lr_t * u with u the paper's update direction, so q_t = |p| / |u| is the paper's trust ratio and p -= lr_t * r * u.  q_t = 1 is the
+// AdamW step bit for bit (1 * d is exact).  Non-finite sums get no special case: a NaN fails both comparisons (r = 1) and reaches p
+// through d, as it does in Adam; the guard is the remedy.
+// lamb_moments_kernel (24 B per parameter: read p, g, m, v; write m, v) walks the tensor table chunk by chunk exactly as
+//   tensor_stats_kernel does (chunk_table / chunk_at), forms d in registers and adds S_p and S_d in that kernel's fixed order: thread j the
+//   vectors j, j + 256, ... of the chunk, then the tensor's trailing elements, the fixed tree, one record {S_p, S_d} per chunk, the
+//   tensor's ticket, the last arrival adding the records in index order.  Whoever finishes a tensor writes trust[t] = q_t and
+//   sums[2 t ..] = {S_p, S_d}.  work = {tickets[T] (padded to 16 B), records[n / STAT_CHUNK + T][2] fp64}, zeroed once by the caller;
+//   the tickets go back to zero.
+// lamb_apply_kernel (16 B per parameter: read p, m, v; write p) walks the same chunks, reads trust[t] once per workgroup and chunk,
+//   forms d again from the stored m and v -- the same device function on the same inputs: the same bits -- and writes p.
+// Both read `hyper` and `ctl` (which may be null) from device memory; with ctl[1] != 0 both return before their first load.  Nothing in
+// either launch changes from step to step: the pair replays from a captured graph and is bit-equal call to call.
+constexpr int LAMB_UNROLL = 2;                             // moments: 121 VGPRs, 4 workgroups per CU (4: 161 VGPRs, 3 per CU -- the 1024-workgroup grid no longer fits)
+constexpr int LAMB_APPLY_UNROLL = 4;                       // apply: 109 VGPRs, 4 per CU
+
+struct LambArgs {
+    float* p; const float* g; float* m; float* v; long n;
+    const float* hyper; const float* ctl;
+    AdamScalars s;                                         // lr, bc1, bc2s come from `hyper` on the device
+    float max_trust;
+    const long* begin; const long* numel; const float* table;      // table: {lr_mult, wd_mult, adapt} per tensor
+    int T, fences;
+    long max_chunks;
+    unsigned* tickets; double* records; float* trust; double* sums;
+};
+
+// the launch's scalars, or false when the step is skipped: before any load of the buffers
+__device__ __forceinline__ bool lamb_scalars(const LambArgs& a, AdamScalars& s) {
+    s = a.s;
+    if (a.ctl != nullptr) {                                // as adamw_kernel's CTL form
+        if (a.ctl[1] != 0.f) return false;
+        s.gscale = s.gscale * a.ctl[0];
+    }
+    s.lr = a.hyper[0]; s.bc1 = a.hyper[1]; s.bc2s = a.hyper[2];
+    return true;
+}
+
+// tensor t's own scalars from the launch's, ONE fp32 multiplication each (as the SEG form's classes)
+__device__ __forceinline__ AdamScalars lamb_tensor_scalars(const AdamScalars& s, const float* table, int t, float& lrwd) {
+    AdamScalars sc = s;
+    sc.lr = s.lr * table[3 * t];
+    sc.wd = s.wd * table[3 * t + 1];
+    lrwd = sc.lr * sc.wd;
+    return sc;
+}
+
+template <int WD>
+__device__ __forceinline__ void lamb_moments_elem(float p, float g, float& m, float& v, const AdamScalars& sc, float lrwd, double& sp, double& sd) {
+    adam_moments<WD>(p, g, m, v, sc);
+    const float d = adam_delta<WD>(p, m, v, sc, lrwd);
+    sp += (double)p * (double)p;
+    sd += (double)d * (double)d;
+}
+
+template <int WD>
+__device__ __forceinline__ void lamb_moments_chunk(const LambArgs& a, const Chunk& ch, const AdamScalars& sc, float lrwd, double& sp, double& sd) {
+    const int tid = threadIdx.x;
+    const long o = ch.b + ch.e0;
+    const f32x4_t* p4 = (const f32x4_t*)(a.p + o);
+    const f32x4_t* g4 = (const f32x4_t*)(a.g + o);
+    f32x4_t* m4 = (f32x4_t*)(a.m + o);
+    f32x4_t* v4 = (f32x4_t*)(a.v + o);
+    long i = tid;
+    for (; i + (LAMB_UNROLL - 1) * OPT_THREADS < ch.nvec; i += LAMB_UNROLL * OPT_THREADS) {
+        f32x4_t pp[LAMB_UNROLL], gg[LAMB_UNROLL], mm[LAMB_UNROLL], vv[LAMB_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LAMB_UNROLL; ++u) {
+            pp[u] = p4[i + u * OPT_THREADS]; gg[u] = g4[i + u * OPT_THREADS]; mm[u] = m4[i + u * OPT_THREADS]; vv[u] = v4[i + u * OPT_THREADS];
+        }
+#pragma unroll
+        for (int u = 0; u < LAMB_UNROLL; ++u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float mk = mm[u][k], vk = vv[u][k];
+                lamb_moments_elem<WD>(pp[u][k], gg[u][k], mk, vk, sc, lrwd, sp, sd);
+                mm[u][k] = mk; vv[u][k] = vk;
+            }
+            m4[i + u * OPT_THREADS] = mm[u]; v4[i + u * OPT_THREADS] = vv[u];
+        }
+    }
+    for (; i < ch.nvec; i += OPT_THREADS) {
+        const f32x4_t pp = p4[i], gg = g4[i];
+        f32x4_t mm = m4[i], vv = v4[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            float mk = mm[k], vk = vv[k];
+            lamb_moments_elem<WD>(pp[k], gg[k], mk, vk, sc, lrwd, sp, sd);
+            mm[k] = mk; vv[k] = vk;
+        }
+        m4[i] = mm; v4[i] = vv;
+    }
+    if (ch.e1 == ch.m && ch.e1 > ch.e0 && tid < (int)(ch.m & 3)) {   // the tensor's trailing elements, in its last chunk
+        const long j = ch.b + (ch.m & ~3L) + tid;
+        float mk = a.m[j], vk = a.v[j];
+        lamb_moments_elem<WD>(a.p[j], a.g[j], mk, vk, sc, lrwd, sp, sd);
+        a.m[j] = mk; a.v[j] = vk;
+    }
+}
+
+// the workgroup's 256 pairs -> thread 0's, in stat_fold's tree: down each 64-lane wave by halving strides, then the four waves in index
+// order.  sh: 4 waves x 2 values.  Every thread calls it.
+__device__ __forceinline__ void lamb_fold(double& sp, double& sd, double (*sh)[2]) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        sp += __shfl_down(sp, off, 64);
+        sd += __shfl_down(sd, off, 64);
+    }
+    const int tid = threadIdx.x;
+    if ((tid & 63) == 0) { sh[tid >> 6][0] = sp; sh[tid >> 6][1] = sd; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < OPT_THREADS / 64; ++w) { sp += sh[w][0]; sd += sh[w][1]; }
+    }
+    __syncthreads();                                       // sh may be written again
+}
+
+// thread 0 of the workgroup that holds tensor t's finished sums
+__device__ __forceinline__ void lamb_finish(const LambArgs& a, int t, float lr_t, double sp, double sd) {
+    double r = 1.0;
+    if (a.table[3 * t + 2] != 0.f && sp > 0.0 && sd > 0.0) r = (double)lr_t * sqrt(sp) / sqrt(sd);
+    if (a.max_trust > 0.f && r > (double)a.max_trust) r = (double)a.max_trust;
+    a.trust[t] = (float)r;
+    a.sums[2L * t] = sp;
+    a.sums[2L * t + 1] = sd;
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void lamb_moments_kernel(LambArgs a) {
+    __shared__ int s_first[STAT_MAX_T + 1];
+    __shared__ int s_part[OPT_THREADS];
+    __shared__ double s_fold[OPT_THREADS / 64][2];
+    __shared__ int s_last;
+    AdamScalars s;
+    if (!lamb_scalars(a, s)) return;                       // a skipped step: m, v, trust, sums, tickets and records keep their bits
+    const int tid = threadIdx.x, T = a.T;
+    long total = chunk_table(a.begin, a.numel, T, a.n, s_first, s_part);
+    if (total > a.max_chunks) total = a.max_chunks;        // as tensor_stats_kernel: nothing is written past the records
+
+    for (long c = blockIdx.x; c < total; c += gridDim.x) {
+        const Chunk ch = chunk_at(c, s_first, a.begin, a.numel, T, a.n);
+        const int t = ch.t, chunks = ch.chunks;
+        float lrwd;
+        const AdamScalars sc = lamb_tensor_scalars(s, a.table, t, lrwd);
+        double sp = 0.0, sd = 0.0;
+        if (sc.wd != 0.f) lamb_moments_chunk<WD_DECOUPLED>(a, ch, sc, lrwd, sp, sd);
+        else lamb_moments_chunk<WD_NONE>(a, ch, sc, 0.f, sp, sd);
+        lamb_fold(sp, sd, s_fold);
+        if (chunks == 1) {                                 // finished here: no record, no ticket
+            if (tid == 0) lamb_finish(a, t, sc.lr, sp, sd);
+            continue;
+        }
+        if (tid == 0) {
+            double* r = a.records + 2 * c;
+            handoff::publish(r, sp); handoff::publish(r + 1, sd);
+        }
+        if (!handoff::arrive<true>([&] { return a.tickets + t; }, [&] { return chunks; }, a.fences, a.fences, &s_last)) continue;
+        // the last of this tensor's workgroups: its records in index order
+        const double* r0 = a.records + 2L * s_first[t];
+        double tp = 0.0, td = 0.0;
+        for (int j = tid; j < chunks; j += OPT_THREADS) {
+            tp += handoff::read(r0 + 2L * j);
+            td += handoff::read(r0 + 2L * j + 1);
+        }
+        lamb_fold(tp, td, s_fold);
+        if (tid == 0) lamb_finish(a, t, sc.lr, tp, td);
+    }
+}
+
+template <int WD>
+__device__ __forceinline__ void lamb_apply_chunk(const LambArgs& a, const Chunk& ch, const AdamScalars& sc, float lrwd, float q) {
+    const int tid = threadIdx.x;
+    const long o = ch.b + ch.e0;
+    f32x4_t* p4 = (f32x4_t*)(a.p + o);
+    const f32x4_t* m4 = (const f32x4_t*)(a.m + o);
+    const f32x4_t* v4 = (const f32x4_t*)(a.v + o);
+    long i = tid;
+    for (; i + (LAMB_APPLY_UNROLL - 1) * OPT_THREADS < ch.nvec; i += LAMB_APPLY_UNROLL * OPT_THREADS) {
+        f32x4_t pp[LAMB_APPLY_UNROLL], mm[LAMB_APPLY_UNROLL], vv[LAMB_APPLY_UNROLL];
+#pragma unroll
+        for (int u = 0; u < LAMB_APPLY_UNROLL; ++u) {
+            pp[u] = p4[i + u * OPT_THREADS]; mm[u] = m4[i + u * OPT_THREADS]; vv[u] = v4[i + u * OPT_THREADS];
+        }
+#pragma unroll
+        for (int u = 0; u < LAMB_APPLY_UNROLL; ++u) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) pp[u][k] = pp[u][k] - q * adam_delta<WD>(pp[u][k], mm[u][k], vv[u][k], sc, lrwd);
+            p4[i + u * OPT_THREADS] = pp[u];
+        }
+    }
+    for (; i < ch.nvec; i += OPT_THREADS) {
+        f32x4_t pp = p4[i];
+        const f32x4_t mm = m4[i], vv = v4[i];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pp[k] = pp[k] - q * adam_delta<WD>(pp[k], mm[k], vv[k], sc, lrwd);
+        p4[i] = pp;
+    }
+    if (ch.e1 == ch.m && ch.e1 > ch.e0 && tid < (int)(ch.m & 3)) {
+        const long j = ch.b + (ch.m & ~3L) + tid;
+        const float pk = a.p[j];
+        a.p[j] = pk - q * adam_delta<WD>(pk, a.m[j], a.v[j], sc, lrwd);
+    }
+}
+
+__global__ __launch_bounds__(OPT_THREADS) void lamb_apply_kernel(LambArgs a) {
+    __shared__ int s_first[STAT_MAX_T + 1];
+    __shared__ int s_part[OPT_THREADS];
+    AdamScalars s;
+    if (!lamb_scalars(a, s)) return;                       // a skipped step: p keeps its bits
+    const int T = a.T;
+    long total = chunk_table(a.begin, a.numel, T, a.n, s_first, s_part);
+    if (total > a.max_chunks) total = a.max_chunks;
+    for (long c = blockIdx.x; c < total; c += gridDim.x) {
+        const Chunk ch = chunk_at(c, s_first, a.begin, a.numel, T, a.n);
+        float lrwd;
+        const AdamScalars sc = lamb_tensor_scalars(s, a.table, ch.t, lrwd);
+        const float q = a.trust[ch.t];                     // one load per workgroup and chunk (uniform)
+        if (sc.wd != 0.f) lamb_apply_chunk<WD_DECOUPLED>(a, ch, sc, lrwd, q);
+        else lamb_apply_chunk<WD_NONE>(a, ch, sc, 0.f, q);
     }
 }
 
@@ -798,6 +1062,56 @@ int mte_tensor_stats(const float* g, const float* p, long n, const long* seg_beg
     const dim3 grid((unsigned)(want > STAT_CAP ? STAT_CAP : want)), block(OPT_THREADS);
     if (p) hipLaunchKernelGGL(tensor_stats_kernel<true>, grid, block, 0, stream, a);
     else hipLaunchKernelGGL(tensor_stats_kernel<false>, grid, block, 0, stream, a);
+    return mte_check_launch();
+}
+
+// Bytes of `work` for mte_lamb_moments over T tensors inside n flat elements (16-byte aligned, zeroed ONCE by the caller): one ticket per
+// tensor, then one record {S_p, S_d} of two fp64 values per chunk.  0 for n <= 0 or T outside 1..4096.
+long mte_lamb_work_bytes(long n, int T) {
+    return (n <= 0 || T < 1 || T > STAT_MAX_T) ? 0 : stat_ticket_bytes(T) + 16L * stat_max_chunks(n, T);
+}
+
+// The first launch of the LAMB step (see lamb_moments_kernel): m and v move as in mte_adamw_step_dev (decoupled), p is only read, and
+// trust[t] = q_t, sums[2 t ..] = {S_p, S_d} are left for every tensor of the table {seg_begin, seg_numel, tensor_table} (DEVICE memory).
+// p, g, m, v and work are 16-byte aligned.  ctl may be null.  A range that leaves [0, n) reads and writes nothing in the flat buffers
+// (its trust is 1, its sums are 0).
+int mte_lamb_moments(const float* p, const float* g, float* m, float* v, long n, const float* hyper, float beta1, float beta2, float eps,
+                     float weight_decay, float gscale, float max_trust, const long* seg_begin, const long* seg_numel, const float* tensor_table,
+                     int T, void* work, float* trust, double* sums, const float* ctl, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!p || !g || !m || !v || !hyper || !seg_begin || !seg_numel || !tensor_table || !work || !trust || !sums) return MTE_ERR_ARG;
+    if (n <= 0 || T < 1 || T > STAT_MAX_T || !(weight_decay >= 0.f) || !(max_trust >= 0.f)) return MTE_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v | (uintptr_t)work) & 15) || ((uintptr_t)sums & 7)) return MTE_ERR_ARG;
+    if (stat_max_chunks(n, T) > 0x7fffffffL) return MTE_ERR_ARG;
+    LambArgs a;
+    a.p = const_cast<float*>(p); a.g = g; a.m = m; a.v = v; a.n = n; a.hyper = hyper; a.ctl = ctl;
+    a.s = {0.f, 0.f, 0.f, beta1, beta2, eps, gscale, weight_decay};
+    a.max_trust = max_trust;
+    a.begin = seg_begin; a.numel = seg_numel; a.table = tensor_table; a.T = T; a.fences = g_mte_handoff_fences;
+    a.max_chunks = stat_max_chunks(n, T);
+    a.tickets = (unsigned*)work; a.records = (double*)((char*)work + stat_ticket_bytes(T)); a.trust = trust; a.sums = sums;
+    const long want = a.max_chunks;
+    hipLaunchKernelGGL(lamb_moments_kernel, dim3((unsigned)(want > STAT_CAP ? STAT_CAP : want)), dim3(OPT_THREADS), 0, stream, a);
+    return mte_check_launch();
+}
+
+// The second launch (see lamb_apply_kernel): p = p - trust[t] * d with d formed again from the stored m and v; m, v and trust are only
+// read.  The same table, hyper, eps, weight_decay and ctl as the mte_lamb_moments launch in front of it.
+int mte_lamb_apply(float* p, const float* m, const float* v, long n, const float* hyper, float eps, float weight_decay, const long* seg_begin,
+                   const long* seg_numel, const float* tensor_table, int T, const float* trust, const float* ctl, hipStream_t stream) {
+    (void)hipGetLastError();   // drop stale errors left by other runtime users (e.g. event queries)
+    if (!p || !m || !v || !hyper || !seg_begin || !seg_numel || !tensor_table || !trust) return MTE_ERR_ARG;
+    if (n <= 0 || T < 1 || T > STAT_MAX_T || !(weight_decay >= 0.f)) return MTE_ERR_ARG;
+    if ((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v) & 15) || stat_max_chunks(n, T) > 0x7fffffffL) return MTE_ERR_ARG;
+    LambArgs a;
+    a.p = p; a.g = nullptr; a.m = const_cast<float*>(m); a.v = const_cast<float*>(v); a.n = n; a.hyper = hyper; a.ctl = ctl;
+    a.s = {0.f, 0.f, 0.f, 0.f, 0.f, eps, 1.f, weight_decay};
+    a.max_trust = 0.f;
+    a.begin = seg_begin; a.numel = seg_numel; a.table = tensor_table; a.T = T; a.fences = 0;
+    a.max_chunks = stat_max_chunks(n, T);
+    a.tickets = nullptr; a.records = nullptr; a.trust = const_cast<float*>(trust); a.sums = nullptr;
+    const long want = a.max_chunks;
+    hipLaunchKernelGGL(lamb_apply_kernel, dim3((unsigned)(want > STAT_CAP ? STAT_CAP : want)), dim3(OPT_THREADS), 0, stream, a);
     return mte_check_launch();
 }
 

@@ -91,7 +91,7 @@ class ModelWrapper(nn.Module):
         return self.current_epoch / self.config.arch.max_epochs
 
     def configure_optimizers(self, process_group=None):
-        """config.model.optimizer.name ('Adam', 'AdamW' or 'SGD') over depth_net.parameters() (param group 'Depth') + StepLR, as the
+        """config.model.optimizer.name ('Adam', 'AdamW', 'LAMB' or 'SGD') over depth_net.parameters() (param group 'Depth') + StepLR, as the
         reference: the keyword arguments are the keys of config.model.optimizer.depth that torch.optim.<name> accepts (filter_args), so
         lr, weight_decay, betas, eps, momentum, dampening and nesterov work when a YAML names them.  The optimizer is the fused flat
         one of that name and carries the bucketed RCCL gradient averaging when torch.distributed is initialised.
@@ -102,16 +102,21 @@ class ModelWrapper(nn.Module):
         the average and its update count; without them the average starts from the loaded weights at count 0.
         config.model.optimizer.tensor_scales (a list of rules {pattern, max_ndim, lr_scale, weight_decay_scale}, see
         resolve_tensor_scales) gives tensors their own multiples of the group's lr and weight_decay -- the fused SEG steps, still one
-        param group; config.model.optimizer.log_tensor_stats = k > 0 makes the trainer print per-tensor gradient statistics."""
+        param group; config.model.optimizer.log_tensor_stats = k > 0 makes the trainer print per-tensor gradient statistics.
+        name 'LAMB' builds FusedLAMB from the keys of `depth` that torch.optim.AdamW accepts; config.model.optimizer.lamb_exclude
+        (rules {pattern, max_ndim}, resolve_lamb_exclude; default [{max_ndim: 1}]: biases and GroupNorm affine tensors) names the
+        tensors that keep plain AdamW arithmetic and lamb_max_trust (0 = no cap) caps the trust ratio; both are read only for LAMB.
+        config.model.optimizer.warmup_steps = W > 0 is the per-step linear lr warm-up of FusedFlatOptimizer (Adam, AdamW, LAMB)."""
         import torch.distributed as dist
-        from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedSGD, broadcast_parameters,
-                                              reference_parameter_names, resolve_tensor_scales)
+        from ..trainers.data_parallel import (FlatParameters, BucketedAllReduce, FusedAdam, FusedLAMB, FusedSGD, broadcast_parameters,
+                                              reference_parameter_names, resolve_lamb_exclude, resolve_tensor_scales)
         opt_cfg = self.config.model.optimizer
-        built = {'Adam': FusedAdam, 'AdamW': FusedAdam, 'SGD': FusedSGD}
+        built = {'Adam': FusedAdam, 'AdamW': FusedAdam, 'LAMB': FusedLAMB, 'SGD': FusedSGD}
         if opt_cfg.name not in built:
             raise NotImplementedError("optimizer '{}' is not built: model.optimizer.name is one of {} (fused flat steps, "
                                       "without amsgrad and maximize)".format(opt_cfg.name, sorted(built)))
-        kwargs = filter_args(getattr(torch.optim, opt_cfg.name), opt_cfg.depth)
+        # LAMB is no torch class: its `depth` keys are AdamW's
+        kwargs = filter_args(getattr(torch.optim, 'AdamW' if opt_cfg.name == 'LAMB' else opt_cfg.name), opt_cfg.depth)
         for key in ('amsgrad', 'maximize'):
             if kwargs.pop(key, False):
                 raise NotImplementedError("{}: true is not built: the fused {} steps are {} without amsgrad and maximize"
@@ -136,10 +141,18 @@ class ModelWrapper(nn.Module):
         # (resolve_tensor_scales); no rule, or rules that leave every tensor at (1, 1), build the optimizer that was always built
         local = dict(self.depth_net.named_parameters())
         rules = opt_cfg.get('tensor_scales') or []
+        name_of = {id(p): n for n, p in local.items()}
+        names, shapes = [name_of[id(p)] for p in flat.natural_params], [tuple(p.shape) for p in flat.natural_params]
         if rules:
-            name_of = {id(p): n for n, p in local.items()}
-            names = [name_of[id(p)] for p in flat.natural_params]
-            kwargs['tensor_scales'] = resolve_tensor_scales(names, [tuple(p.shape) for p in flat.natural_params], rules)
+            kwargs['tensor_scales'] = resolve_tensor_scales(names, shapes, rules)
+        if opt_cfg.name == 'LAMB':
+            # model.optimizer.lamb_exclude / lamb_max_trust: read for this name only
+            exclude = opt_cfg.get('lamb_exclude')
+            kwargs['adapt'] = resolve_lamb_exclude(names, shapes, [{'max_ndim': 1}] if exclude is None else exclude)
+            kwargs['max_trust'] = float(opt_cfg.get('lamb_max_trust') or 0.0)
+            kwargs.pop('decoupled_weight_decay', None)       # always decoupled
+        if int(opt_cfg.get('warmup_steps') or 0):
+            kwargs['warmup_steps'] = int(opt_cfg.get('warmup_steps'))
         optimizer = built[opt_cfg.name](flat, reducer=reducer, name='Depth', clip_grad_norm=float(opt_cfg.clip_grad_norm or 0.0),
                                         skip_nonfinite=bool(opt_cfg.skip_nonfinite_steps), accumulate_grad_batches=accumulate,
                                         ema_decay=float(opt_cfg.get('ema_decay') or 0.0),

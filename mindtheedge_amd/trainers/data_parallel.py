@@ -1,4 +1,4 @@
-"""Flat parameter/gradient storage, bucketed gradient all-reduce (RCCL over xGMI) and the fused optimizers (Adam, AdamW, SGD).
+"""Flat parameter/gradient storage, bucketed gradient all-reduce (RCCL over xGMI) and the fused optimizers (Adam, AdamW, LAMB, SGD).
 
 This is the MI355X-native replacement of the reference's dead Horovod path (``hvd.DistributedOptimizer`` in
 packnet_sfm/trainers/horovod_trainer.py:53-55: average every parameter gradient across ranks, overlapped with
@@ -286,6 +286,43 @@ def tensor_scale_classes(pairs):
     return classes, class_of
 
 
+def match_tensor_rule(names, shapes, pattern=None, max_ndim=None):
+    """The matching language of the per-tensor rules (tensor_scales, lamb_exclude): the positions of the tensors that a rule reaches --
+    re.search(pattern, name) finds something (no pattern: every name) and, with max_ndim, the tensor has at most that many dimensions"""
+    import re
+    rx = re.compile(pattern) if pattern is not None else None
+    return [i for i, (name, shape) in enumerate(zip(names, shapes))
+            if not ((rx is not None and not rx.search(name)) or (max_ndim is not None and len(shape) > int(max_ndim)))]
+
+
+def resolve_lamb_exclude(names, shapes, rules):
+    """model.optimizer.lamb_exclude -> one ``adapt`` flag per tensor (FusedLAMB): a tensor that any rule {pattern, max_ndim} matches
+    (match_tensor_rule, resolve_tensor_scales' language) is excluded from the layer-wise adaptation -- False: plain AdamW arithmetic, trust
+    ratio 1 -- and every other tensor is adapted.  [] adapts everything.  An unknown key, a rule with neither key and a rule that matches
+    no trained tensor are ValueErrors."""
+    adapt = [True] * len(names)
+    for rule in (rules or ()):
+        rule = dict(rule)
+        if set(rule) - {'pattern', 'max_ndim'} or not any(rule.get(k) is not None for k in ('pattern', 'max_ndim')):
+            raise ValueError("lamb_exclude rule {}: keys are pattern and max_ndim, and a rule names at least one".format(rule))
+        hits = match_tensor_rule(names, shapes, rule.get('pattern'), rule.get('max_ndim'))
+        if not hits:
+            raise ValueError("lamb_exclude rule with pattern {!r} (max_ndim {}) matches no trained tensor".format(
+                rule.get('pattern'), rule.get('max_ndim')))
+        for i in hits:
+            adapt[i] = False
+    return adapt
+
+
+def warmup_factor(k, warmup_steps):
+    """The linear learning-rate warm-up's factor at optimizer step k (1-based): min(1, k / W) in double precision, and exactly 1.0
+    with W <= 0 (off).  A pure function of its arguments."""
+    w = int(warmup_steps)
+    if w <= 0:
+        return 1.0
+    return min(1.0, float(k) / float(w))
+
+
 def resolve_tensor_scales(names, shapes, rules):
     """model.optimizer.tensor_scales -> one (lr_scale, weight_decay_scale) per tensor.
 
@@ -295,7 +332,6 @@ def resolve_tensor_scales(names, shapes, rules):
     matching rule that names the attribute gives its value; a tensor that no such rule reaches gets 1.  A rule that matches no tensor
     at all is a ValueError that shows its pattern (a typo must not pass silently), as are an unknown key, a rule that names neither
     attribute, a negative or non-finite multiplier and more than MAX_SCALE_CLASSES distinct pairs."""
-    import re
     keys = ('lr_scale', 'weight_decay_scale')
     out = [[None, None] for _ in names]
     for rule in (rules or ()):
@@ -305,16 +341,12 @@ def resolve_tensor_scales(names, shapes, rules):
             raise ValueError("tensor_scales rule {}: keys are pattern, max_ndim, lr_scale, weight_decay_scale, and a rule names at least "
                              "one of the two scales".format(rule))
         pattern, max_ndim = rule.get('pattern'), rule.get('max_ndim')
-        rx = re.compile(pattern) if pattern is not None else None
-        hit = False
-        for i, (name, shape) in enumerate(zip(names, shapes)):
-            if (rx is not None and not rx.search(name)) or (max_ndim is not None and len(shape) > int(max_ndim)):
-                continue
-            hit = True
+        hits = match_tensor_rule(names, shapes, pattern, max_ndim)
+        for i in hits:
             for j, k in enumerate(keys):
                 if rule.get(k) is not None and out[i][j] is None:
                     out[i][j] = float(rule[k])
-        if not hit:
+        if not hits:
             raise ValueError("tensor_scales rule with pattern {!r} (max_ndim {}) matches no trained tensor".format(pattern, max_ndim))
     pairs = [(1.0 if a is None else a, 1.0 if b is None else b) for a, b in out]
     tensor_scale_classes(pairs)                              # the multipliers' and the class limit's ValueErrors
@@ -382,14 +414,26 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
     pair (1, 1), is OFF: no table, no attribute, and ``_launch`` / ``_launch_ctl`` are the launches described above.
 
     ``tensor_stats()``: per-tensor gradient norm, largest finite |g|, count of non-finite gradient elements and weight norm in ONE
-    read-only launch (mte_tensor_stats) and one host read, whether or not ``tensor_scales`` is set; never launched by ``step()``."""
+    read-only launch (mte_tensor_stats) and one host read, whether or not ``tensor_scales`` is set; never launched by ``step()``.
+
+    Per-step linear learning-rate warm-up (``warmup_steps`` = W > 0, for the classes with HAS_STEP, whose step count comes back from
+    a checkpoint): step k (1-based, ``steps`` after counting) uploads lr * warmup_factor(k, W) = lr * min(1, k / W), formed in double,
+    as ``hyper[0]``.  ``param_groups[0]['lr']`` is never changed, so StepLR, checkpoints and ``tensor_scales`` (which multiply
+    ``hyper[0]`` on the device) compose with it.  W is configuration, not ``state_dict()``.  With W = 0 -- the default -- nothing is
+    multiplied: ``hyper`` is formed exactly as it always was."""
 
     HAS_STEP = False                                        # torch keeps a 'step' entry per tensor (Adam) or none (SGD)
     LEGACY_FLAT = False                                      # reads the flat {'steps', <buffers>} layout of earlier builds (Adam only)
     LOAD_KEYS = ('lr', 'initial_lr')
 
     def __init__(self, flat, defaults, reducer=None, name='Depth', clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1,
-                 ema_decay=0.0, ema_warmup=True, tensor_scales=None):
+                 ema_decay=0.0, ema_warmup=True, tensor_scales=None, warmup_steps=0):
+        if int(warmup_steps) != warmup_steps or int(warmup_steps) < 0:
+            raise ValueError("Invalid warmup_steps value: {} (an integer >= 0; 0 = off)".format(warmup_steps))
+        if int(warmup_steps) > 0 and not self.HAS_STEP:
+            raise ValueError("warmup_steps > 0 needs an optimizer whose step count is part of its checkpoint (Adam, AdamW, LAMB): {} keeps "
+                             "no step entry, so a resumed run could not know where in the warm-up it stands".format(type(self).__name__))
+        self.warmup_steps = int(warmup_steps)
         if not 0.0 <= float(ema_decay) < 1.0:
             raise ValueError("Invalid ema_decay value: {} (in [0, 1); 0 = off)".format(ema_decay))
         if tensor_scales is not None:
@@ -566,6 +610,8 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         else:
             self.steps += 1
             self._last_gscale = float(gscale)
+            if self.warmup_steps > 0:                        # the warm-up reaches the host-scalar entry points through a copy of the group
+                g = dict(g, lr=float(g['lr']) * warmup_factor(self.steps, self.warmup_steps))
             self._host_step(K, g, gscale)                  # no CPU form: raises MteError on host buffers
         if self.flatp.grad.is_cuda:
             K.prefetch_weight_packs()                       # next step's kernel-ready weight packs, off the critical path
@@ -577,6 +623,8 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         host-scalar entry point) -- called by step(), or by a graph-replaying caller right before each replay."""
         self.steps += 1
         vals = self._hyper_values(self.param_groups[0])
+        if self.warmup_steps > 0:                            # only then: without a warm-up nothing is multiplied
+            vals[0] = vals[0] * warmup_factor(self.steps, self.warmup_steps)
         if self.hyper.is_cuda and not os.environ.get("MTE_ADAM_PAGEABLE_HYPER"):
             # a copy from pageable memory makes the host wait for the stream (every step: the GPU then idles while the host catches
             # up with the next forward pass); a ring of pinned slots keeps the upload asynchronous.  Each slot carries the event of
@@ -790,14 +838,14 @@ class FusedAdam(FusedFlatOptimizer):
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, reducer=None, name='Depth', weight_decay=0.0,
                  decoupled_weight_decay=False, clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0,
-                 ema_warmup=True, tensor_scales=None):
+                 ema_warmup=True, tensor_scales=None, warmup_steps=0):
         if not 0.0 <= float(weight_decay):
             raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
         super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
                                     capturable=False, differentiable=False, fused=None,
                                     decoupled_weight_decay=bool(decoupled_weight_decay)), reducer=reducer, name=name,
                          clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales, warmup_steps=warmup_steps)
         self.exp_avg = torch.zeros_like(flat.flat)
         self.exp_avg_sq = torch.zeros_like(flat.flat)
 
@@ -841,6 +889,138 @@ class FusedAdam(FusedFlatOptimizer):
                               eps=g['eps'], weight_decay=g['weight_decay'], decoupled=g['decoupled_weight_decay'], gscale=gscale)
 
 
+class FusedLAMB(FusedFlatOptimizer):
+    """LAMB (You et al., "Large Batch Optimization for Deep Learning"): AdamW whose per-tensor update is rescaled by the trust ratio
+    ||w|| / ||update||, as TWO HBM-bound launches over the flat buffers with no scratch buffer -- mte_lamb_moments (24 B/parameter: read
+    p, g, m, v; write m, v; the per-tensor fp64 sums of p^2 and of the squared delta in a fixed order; ``trust``) and mte_lamb_apply
+    (16 B/parameter: read p, m, v; write p).  Per element the arithmetic is the decoupled AdamW step's, and a tensor with trust ratio 1 --
+    every excluded tensor -- gets mte_adamw_step_dev's result bit for bit (tests/lamb_ref.py states the step in float64).
+
+    The group is torch.optim.AdamW's key set with ``decoupled_weight_decay=True``: the checkpoint layout, the reference's index space,
+    StepLR and ``load_state_dict`` are AdamW's, and an AdamW checkpoint warm-starts LAMB (``exp_avg``, ``exp_avg_sq``, ``step``).
+    ``adapt``: one bool per trained tensor in ``natural_params`` order (default: all True); False = plain AdamW arithmetic for that tensor
+    (biases and normalisation affine tensors, by the usual practice: model.optimizer.lamb_exclude).  ``max_trust`` > 0 caps the ratio.
+    ``tensor_scales`` pairs go into the per-tensor table {lr_mult, wd_mult, adapt} in device memory: the SEG block-class tables are never
+    built for this class and there is no 16-class limit.  All three are configuration, not ``state_dict()``.
+
+    ``step()`` launches the pair on the current stream, behind the norm launch when clipping or the guard is on (both launches read
+    ``ctl``: the clip coefficient scales the gradient, a skipped step changes nothing).  Accumulation, the weight EMA, ``no_sync``,
+    ``advance()``, the pinned ``hyper`` ring, the weights epoch and the error poll are FusedFlatOptimizer's, unchanged; both launches are
+    the same every step and replay from a HIP graph.  Run it with ``warmup_steps`` (see FusedFlatOptimizer).
+
+    Across ranks the sums are taken after the all-reduce has finished, over the summed gradient buffer (with gscale = 1/world) and the
+    weights; the all-reduce leaves the same bits on every rank and the sums have one order, so every rank forms the same ``trust`` and
+    the weights stay bit-equal across ranks.
+
+    ``trust_ratios()`` reports the last step's ratios (one host read; never called by ``step()``)."""
+
+    HAS_STEP = True
+    LOAD_KEYS = ('lr', 'betas', 'eps', 'initial_lr', 'weight_decay')
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.01, reducer=None, name='Depth', adapt=None, max_trust=0.0,
+                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True, tensor_scales=None,
+                 warmup_steps=0):
+        import math
+        if not 0.0 <= float(weight_decay):
+            raise ValueError("Invalid weight_decay value: {}".format(weight_decay))
+        if not float(max_trust) >= 0.0:
+            raise ValueError("Invalid max_trust value: {} (0 = no cap)".format(max_trust))
+        n_t = len(flat.natural_params)
+        adapt = [True] * n_t if adapt is None else [bool(a) for a in adapt]
+        scales = [(1.0, 1.0)] * n_t if tensor_scales is None else [(float(a), float(b)) for a, b in tensor_scales]
+        if len(adapt) != n_t or len(scales) != n_t:
+            raise ValueError("adapt / tensor_scales hold {} / {} entries for {} trained tensors".format(len(adapt), len(scales), n_t))
+        for i, pair in enumerate(scales):
+            if not all(math.isfinite(x) and x >= 0.0 for x in pair):
+                raise ValueError("Invalid tensor_scales pair {} for tensor {}: multipliers are finite and >= 0".format(pair, i))
+        # tensor_scales never reaches the base class: no SEG tables, no class limit
+        super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=False, maximize=False, foreach=None,
+                                    capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True), reducer=reducer,
+                         name=name, clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite,
+                         accumulate_grad_batches=accumulate_grad_batches, ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=None,
+                         warmup_steps=warmup_steps)
+        self.adapt, self.max_trust, self.lamb_scales = adapt, float(max_trust), scales
+        self.exp_avg = torch.zeros_like(flat.flat)
+        self.exp_avg_sq = torch.zeros_like(flat.flat)
+        self._lamb_tables = None                             # device tables and work buffer: made at the first launch, then kept
+
+    def state_buffers(self):
+        return [('exp_avg', self.exp_avg), ('exp_avg_sq', self.exp_avg_sq)]
+
+    def _hyper_values(self, g):
+        """Adam's: lr, 1 - b1^t, sqrt(1 - b2^t); the step's own learning rate (warm-up included) is kept for trust_ratios()"""
+        vals = FusedAdam._hyper_values(self, g)
+        self._step_lr = vals[0] * warmup_factor(self.steps, self.warmup_steps)
+        return vals
+
+    def _tables(self, K):
+        """(begins, numels, {lr_mult, wd_mult, adapt} per tensor, work, trust, sums) in FLAT order on the device; ``trust`` (T floats) and
+        ``sums`` (2 T doubles) are views of ONE buffer, so that trust_ratios() is one host read"""
+        if self._lamb_tables is None:
+            flat = self.flatp
+            dev = flat.flat.device
+            segs = flat.segments()
+            T = len(segs)
+            begins, numels = flat.segments(device=dev)
+            table = torch.tensor([x for _, _, slot in segs for x in (self.lamb_scales[slot][0], self.lamb_scales[slot][1],
+                                                                      1.0 if self.adapt[slot] else 0.0)], dtype=torch.float32, device=dev)
+            work = torch.zeros((int(K.lib.mte_lamb_work_bytes(flat.total, T)) + 7) // 8, dtype=torch.float64, device=dev)   # zeroed ONCE
+            out = torch.zeros(2 * T + (T + 1) // 2, dtype=torch.float64, device=dev)
+            self._lamb_out = out
+            self._lamb_tables = (begins, numels, table, work, out[2 * T:].view(torch.float32)[:T], out[:2 * T])
+        return self._lamb_tables
+
+    def _pair(self, K, g, gscale, ctl, stream):
+        K._require_gpu(self.flatp.flat)
+        begins, numels, table, work, trust, sums = self._tables(K)
+        flat, T = self.flatp, len(self.flatp.params)
+        b1, b2 = float(g['betas'][0]), float(g['betas'][1])
+        eps, wd = float(g['eps']), float(g['weight_decay'])
+        K.lib.mte_lamb_moments(flat.flat.data_ptr(), flat.grad.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), flat.total,
+                               self.hyper.data_ptr(), b1, b2, eps, wd, gscale, self.max_trust, begins.data_ptr(), numels.data_ptr(),
+                               table.data_ptr(), T, work.data_ptr(), trust.data_ptr(), sums.data_ptr(), ctl, stream)
+        K.lib.mte_lamb_apply(flat.flat.data_ptr(), self.exp_avg.data_ptr(), self.exp_avg_sq.data_ptr(), flat.total, self.hyper.data_ptr(), eps,
+                             wd, begins.data_ptr(), numels.data_ptr(), table.data_ptr(), T, trust.data_ptr(), ctl, stream)
+
+    def _launch(self, K, g, gscale, stream):
+        self._pair(K, g, gscale, None, stream)
+
+    def _launch_ctl(self, K, g, gscale, stream):
+        self._pair(K, g, gscale, self.ctl.data_ptr(), stream)
+
+    def _host_step(self, K, g, gscale):
+        """no CPU form of the step: MteError on host buffers, as the siblings"""
+        self._pair(K, g, gscale, None, None)
+
+    @torch.no_grad()
+    def trust_ratios(self):
+        """One dict per trained tensor, in the order of the reference's numbering (set_index_space; positional names without it):
+        {'name', 'trust_ratio' (q_t as the last step applied it), 'weight_norm' (sqrt(S_p), the weights BEFORE that step), 'update_norm'
+        (sqrt(S_d) / lr_t: the norm of the paper's update direction; 0.0 where lr_t is 0), 'adapted'}.  ONE host read of what the
+        last step's mte_lamb_moments launch left; no launch.  Before the first step every ratio reads 0."""
+        import math
+        import numpy as np
+        from .. import kernels as K
+        K._require_gpu(self.flatp.flat)
+        self._tables(K)
+        T = len(self.flatp.params)
+        host = self._lamb_out.cpu()                           # the one host read
+        sums, trust = host[:2 * T].view(-1, 2).tolist(), host[2 * T:].view(torch.float32)[:T].tolist()
+        row_of = {id(p): (q, sp, sd) for p, q, (sp, sd) in zip(self.flatp.params, trust, sums)}
+        slot_of = {id(p): i for i, p in enumerate(self.flatp.natural_params)}
+        lr = float(np.float32(getattr(self, '_step_lr', 0.0)))       # hyper[0] of the last step
+        res = []
+        for pos, (name, p, _) in enumerate(self._space()):
+            if p is None:
+                continue
+            q, sp, sd = row_of[id(p)]
+            slot = slot_of[id(p)]
+            lr_t = float(np.float32(lr) * np.float32(self.lamb_scales[slot][0]))
+            res.append({'name': name if name is not None else str(pos), 'trust_ratio': q, 'weight_norm': math.sqrt(sp) if sp >= 0 else sp,
+                        'update_norm': (math.sqrt(sd) if sd >= 0 else sd) / lr_t if lr_t > 0.0 else 0.0, 'adapted': bool(self.adapt[slot])})
+        return res
+
+
 class FusedSGD(FusedFlatOptimizer):
     """torch.optim.SGD(lr, momentum, dampening, weight_decay, nesterov) as ONE HBM-bound kernel over the flat buffers: 20 B/parameter
     with momentum (read p,g,buf; write p,buf), 12 B without (no buffer exists then).  torch's first-step rule (buf = g') reaches the
@@ -852,7 +1032,8 @@ class FusedSGD(FusedFlatOptimizer):
     LOAD_KEYS = ('lr', 'initial_lr', 'momentum', 'dampening', 'weight_decay', 'nesterov')
 
     def __init__(self, flat, lr=1e-3, momentum=0.0, dampening=0.0, weight_decay=0.0, nesterov=False, reducer=None, name='Depth',
-                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True, tensor_scales=None):
+                 clip_grad_norm=0.0, skip_nonfinite=False, accumulate_grad_batches=1, ema_decay=0.0, ema_warmup=True, tensor_scales=None,
+                 warmup_steps=0):
         if float(lr) < 0.0 or float(momentum) < 0.0 or float(weight_decay) < 0.0:
             raise ValueError("Invalid lr / momentum / weight_decay: {} / {} / {}".format(lr, momentum, weight_decay))
         if nesterov and (momentum <= 0 or dampening != 0):
@@ -860,7 +1041,7 @@ class FusedSGD(FusedFlatOptimizer):
         super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=bool(nesterov),
                                     maximize=False, foreach=None, differentiable=False, fused=None), reducer=reducer, name=name,
                          clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_grad_batches=accumulate_grad_batches,
-                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales)
+                         ema_decay=ema_decay, ema_warmup=ema_warmup, tensor_scales=tensor_scales, warmup_steps=warmup_steps)
         self.momentum_buffer = None
         self.state_buffers()
 

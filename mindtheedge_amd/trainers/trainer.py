@@ -54,14 +54,18 @@ def _with_group_end(dataloader, k):
             yield batch, last
 
 
-def tensor_stats_lines(stats, k):
+def tensor_stats_lines(stats, k, trust=None):
     """The log lines of model.optimizer.log_tensor_stats = k from FusedFlatOptimizer.tensor_stats(): the k tensors with the largest
-    gradient norm (non-finite norms first), then every tensor whose gradient holds an inf or a NaN, by name"""
+    gradient norm (non-finite norms first), then every tensor whose gradient holds an inf or a NaN, by name.  ``trust``
+    (FusedLAMB.trust_ratios(), else None): each tensor line ends with that tensor's trust ratio; without it the lines are what they were."""
     def key(s):
         return (0, 0.0) if s['grad_norm'] != s['grad_norm'] or s['grad_norm'] == float('inf') else (1, -s['grad_norm'])
     lines = ['  grad top {} | {} | norm {:.4g} | amax {:.4g} | weight norm {:.4g} | lr x{:g} | wd x{:g}'.format(
         i + 1, s['name'], s['grad_norm'], s['grad_amax'], s['weight_norm'], s['lr_scale'], s['weight_decay_scale'])
         for i, s in enumerate(sorted(stats, key=key)[:int(k)])]
+    if trust is not None:
+        q_of = {r['name']: r['trust_ratio'] for r in trust}
+        lines = [line + ' | trust {:.4g}'.format(q_of[s['name']]) for line, s in zip(lines, sorted(stats, key=key)[:int(k)])]
     lines += ['  grad non-finite | {} | {} of {} elements'.format(s['name'], s['nonfinite'], s['numel']) for s in stats if s['nonfinite'] > 0]
     return lines
 
@@ -194,7 +198,8 @@ class Trainer:
                 if getattr(module, 'log_tensor_stats', 0) > 0 and hasattr(optimizer, 'tensor_stats'):
                     # model.optimizer.log_tensor_stats: one more read-only launch and host read per log line; the gradient buffer still
                     # holds this batch's gradient (zero_grad comes with the next batch)
-                    for extra in tensor_stats_lines(optimizer.tensor_stats(), module.log_tensor_stats):
+                    trust = optimizer.trust_ratios() if hasattr(optimizer, 'trust_ratios') else None      # LAMB only: one more host read
+                    for extra in tensor_stats_lines(optimizer.tensor_stats(), module.log_tensor_stats, trust):
                         print(extra, flush=True)
         if n:
             last = read()

@@ -36,8 +36,15 @@ _DEFAULTS = {
         # multiples of the group's lr / weight_decay (first matching rule per attribute; trainers/data_parallel.py::resolve_tensor_scales).
         # log_tensor_stats (0 = off): k > 0 prints, after each training log line, the k tensors with the largest gradient norm and every tensor
         # whose gradient holds an inf or a NaN.
+        # name 'LAMB': AdamW with layer-wise trust ratios (FusedLAMB; `depth` takes torch.optim.AdamW's keys), for the large effective batches
+        # that accumulate_grad_batches reaches.  lamb_exclude: rules {pattern, max_ndim} in tensor_scales' matching language; a matching tensor
+        # keeps plain AdamW arithmetic (the default excludes the tensors of at most one dimension: biases and GroupNorm affine tensors;
+        # [] adapts everything).  lamb_max_trust (0 = no cap): upper limit of the trust ratio.  Both are read only when name is 'LAMB'.
+        # warmup_steps (0 = off): W > 0 multiplies the lr the step kernels see by min(1, k / W) at optimizer step k; the group's lr, and with
+        # it StepLR and the checkpoint, is untouched (Adam, AdamW, LAMB; SGD keeps no step count in its checkpoint and raises).
         'optimizer': {'name': 'Adam', 'depth': {'lr': 0.0002, 'weight_decay': 0.0}, 'clip_grad_norm': 0.0, 'skip_nonfinite_steps': False,
-                      'ema_decay': 0.0, 'ema_warmup': True, 'ema_validate': True, 'tensor_scales': [], 'log_tensor_stats': 0},
+                      'ema_decay': 0.0, 'ema_warmup': True, 'ema_validate': True, 'tensor_scales': [], 'log_tensor_stats': 0,
+                      'warmup_steps': 0, 'lamb_exclude': [{'max_ndim': 1}], 'lamb_max_trust': 0.0},
         'scheduler': {'name': 'StepLR', 'step_size': 10, 'gamma': 0.5},
         'params': {'crop': '', 'min_depth': 0.0, 'max_depth': 80.0, 'scale_output': 'resize'},     # default_config.py:84-87
         'loss': {'supervised_method': 'sparse-l1', 'supervised_num_scales': 4, 'supervised_loss_weight': 0.9,
