@@ -353,6 +353,30 @@ def resolve_tensor_scales(names, shapes, rules):
     return pairs
 
 
+class _PinnedRing:
+    """Asynchronous upload of a few per-step floats.  A copy from pageable memory makes the host wait for the stream (every step: the GPU
+    then idles while the host catches up with the next forward pass); a ring of pinned slots keeps the upload asynchronous.  Each slot
+    carries the event of its last upload and is rewritten only after that copy has executed (with HIP-graph replay or an unthrottled
+    loop the host can run more than 16 steps ahead of the device; the wait is almost always already satisfied)."""
+    SLOTS = 16
+
+    def __init__(self, width):
+        self.pinned = torch.empty((self.SLOTS, width), dtype=torch.float32).pin_memory()
+        self.events = [None] * self.SLOTS
+
+    def upload(self, dst, values, index):
+        i = index % self.SLOTS
+        if self.events[i] is not None:
+            self.events[i].synchronize()
+        slot = self.pinned[i]
+        for k, v in enumerate(values):
+            slot[k] = v
+        dst.copy_(slot, non_blocking=True)
+        ev = self.events[i] or torch.cuda.Event()
+        ev.record()
+        self.events[i] = ev
+
+
 class FusedFlatOptimizer(torch.optim.Optimizer):
     """What the fused optimizers share: ONE HBM-bound kernel over the flat buffers per step, with everything around it -- the reducer's
     wait and its gradient scale, the gradient sink, the side stream, the weight-pack epoch and prefetch, the device error poll, the three
@@ -464,7 +488,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         self._group_keys = tuple(defaults)
         self.steps = 0
         self.hyper = torch.zeros(3, dtype=torch.float32, device=flat.flat.device)    # read by the kernel (see _hyper_values)
-        self._hyper_pinned = None
+        self._hyper_ring = None
         if self.clip_grad_norm > 0.0 or self.skip_nonfinite:
             # only then: the default optimizer has no `ctl` attribute, no work buffer and no norm launch
             self.ctl = torch.zeros(4, dtype=torch.float32, device=flat.flat.device)
@@ -478,7 +502,7 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
             # only then: the default optimizer has no average, no `ema_scal` and no EMA launch
             flat.enable_ema()
             self.ema_scal = torch.zeros(2, dtype=torch.float32, device=flat.flat.device)     # {d32, omd32}, read by the kernel
-            self._ema_pinned = None
+            self._ema_ring = None
 
     def grad_stats(self):
         """{'grad_norm', 'clip_coef', 'skipped', 'skipped_steps'} of the last step as Python numbers: ONE host read (it waits for the
@@ -626,41 +650,18 @@ class FusedFlatOptimizer(torch.optim.Optimizer):
         if self.warmup_steps > 0:                            # only then: without a warm-up nothing is multiplied
             vals[0] = vals[0] * warmup_factor(self.steps, self.warmup_steps)
         if self.hyper.is_cuda and not os.environ.get("MTE_ADAM_PAGEABLE_HYPER"):
-            # a copy from pageable memory makes the host wait for the stream (every step: the GPU then idles while the host catches
-            # up with the next forward pass); a ring of pinned slots keeps the upload asynchronous.  Each slot carries the event of
-            # its last upload and is rewritten only after that copy has executed (with HIP-graph replay or an unthrottled loop the host
-            # can run more than 16 steps ahead of the device; the wait is almost always already satisfied)
-            if self._hyper_pinned is None:
-                self._hyper_pinned = torch.empty((16, 3), dtype=torch.float32).pin_memory()
-                self._hyper_events = [None] * 16
-            i = self.steps % 16
-            if self._hyper_events[i] is not None:
-                self._hyper_events[i].synchronize()
-            slot = self._hyper_pinned[i]
-            slot[0], slot[1], slot[2] = vals
-            self.hyper.copy_(slot, non_blocking=True)
-            ev = self._hyper_events[i] or torch.cuda.Event()
-            ev.record()
-            self._hyper_events[i] = ev
+            if self._hyper_ring is None:
+                self._hyper_ring = _PinnedRing(3)
+            self._hyper_ring.upload(self.hyper, vals, self.steps)
         else:
             self.hyper.copy_(torch.tensor(vals, dtype=torch.float32), non_blocking=True)
         if self.ema_decay > 0.0:
             self.ema_updates += 1
             pair = ema_decay_pair(self.ema_updates, self.ema_decay, self.ema_warmup)
             if self.ema_scal.is_cuda:
-                # a pinned ring of its own, as hyper's: each slot waits for its last upload before it is rewritten
-                if self._ema_pinned is None:
-                    self._ema_pinned = torch.empty((16, 2), dtype=torch.float32).pin_memory()
-                    self._ema_events = [None] * 16
-                i = self.ema_updates % 16
-                if self._ema_events[i] is not None:
-                    self._ema_events[i].synchronize()
-                slot = self._ema_pinned[i]
-                slot[0], slot[1] = pair
-                self.ema_scal.copy_(slot, non_blocking=True)
-                ev = self._ema_events[i] or torch.cuda.Event()
-                ev.record()
-                self._ema_events[i] = ev
+                if self._ema_ring is None:
+                    self._ema_ring = _PinnedRing(2)
+                self._ema_ring.upload(self.ema_scal, pair, self.ema_updates)
             else:
                 self.ema_scal.copy_(torch.tensor(pair, dtype=torch.float32))
 

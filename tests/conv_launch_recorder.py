@@ -8,10 +8,11 @@ the case (the driver's input line) and what was launched.  tests/test_conv_launc
 tests/p3_launch_table.json (tests/test_p3_launch_table_cpu.py).  --patch: the same for conv_patch.hip with tests/patch_launch_driver.cpp (the LDS-patch convolution's
 six launching entry points and its queries) and tests/patch_launch_table.json (tests/test_patch_launch_table_cpu.py).  --wgrad: the same for mte_conv2d_wgrad and its
 query (conv_igemm.hip, conv_wgrad9.hip) with tests/wgrad_launch_driver.cpp and tests/wgrad_launch_table.json (tests/test_wgrad_launch_table_cpu.py); the shim answers
-the device query with the CU count of the case.
+the device query with the CU count of the case.  --optim: the same for optim.hip with tests/optim_launch_driver.cpp (the optimizer family's 16 launching entry points
+and three work-buffer queries; the kernels' plain arguments are recorded too) and tests/optim_launch_table.json (tests/test_optim_launch_table_cpu.py).
 
-    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
-    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad | --optim] --write            regenerate the table from the working tree (after a dispatch rule was changed ON PURPOSE)
+    python tests/conv_launch_recorder.py [--gn | --p3 | --patch | --wgrad | --optim] --csrc DIR --out F  record another checkout's csrc/ (the parent's, to compare)
 """
 import argparse
 import json
@@ -28,17 +29,19 @@ GN_TABLE = os.path.join(TESTS, "gn_launch_table.json")
 P3_TABLE = os.path.join(TESTS, "p3_launch_table.json")
 PATCH_TABLE = os.path.join(TESTS, "patch_launch_table.json")
 WGRAD_TABLE = os.path.join(TESTS, "wgrad_launch_table.json")
+OPTIM_TABLE = os.path.join(TESTS, "optim_launch_table.json")
 HIPCC = os.environ.get("HIPCC") or ("/opt/rocm/bin/hipcc" if os.path.exists("/opt/rocm/bin/hipcc") else "hipcc")
 SPLITK_SLABS = 8                    # kernels.SPLITK_SLABS (the test checks that they agree)
 BF16, F32 = 0, 1
 SOLO = 2                            # MTE_CONV_SOLO bit of `accumulate`
 
 
-def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False, wgrad=False):
+def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False, wgrad=False, optim=False):
     """-> path of the recorder program built from `csrc` (dev: with -DMTE_DEV, the build that has the knobs; gn: the GroupNorm driver and norm_act.hip with it;
-    p3: the conv3d pack / unpack driver and pack3d.hip; patch: the LDS-patch convolution driver and conv_patch.hip; wgrad: the weight-gradient driver.
+    p3: the conv3d pack / unpack driver and pack3d.hip; patch: the LDS-patch convolution driver and conv_patch.hip; wgrad: the weight-gradient driver;
+    optim: the optimizer driver and optim.hip, with the kernels' plain arguments recorded too.
     conv_wgrad9.hip is linked into all of them: conv_igemm.hip launches through it)"""
-    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "patch_" if patch else "wgrad_" if wgrad else "") + ("recorder_dev" if dev else "recorder"))
+    exe = os.path.join(out_dir, ("gn_" if gn else "p3_" if p3 else "patch_" if patch else "wgrad_" if wgrad else "optim_" if optim else "") + ("recorder_dev" if dev else "recorder"))
     cmd = [HIPCC, "--cuda-host-only", "-fuse-cuid=none", "-Wl,--allow-multiple-definition", "-std=c++17", "-O1", "-Wno-unused-value", "-I", csrc, "-I", TESTS, "-include", os.path.join(TESTS, "conv_launch_shim.hpp")]
     cmd += ["-DMTE_DEV"] if dev else []
     cmd += list(extra) + [os.path.join(csrc, "conv_igemm.hip"), os.path.join(csrc, "conv_igemm8.hip"), os.path.join(csrc, "conv_wgrad9.hip")]
@@ -50,6 +53,8 @@ def build(out_dir, dev, csrc=CSRC, extra=(), gn=False, p3=False, patch=False, wg
         cmd += [os.path.join(csrc, "conv_patch.hip"), os.path.join(TESTS, "patch_launch_driver.cpp")]
     elif wgrad:
         cmd += [os.path.join(TESTS, "wgrad_launch_driver.cpp")]
+    elif optim:
+        cmd += ["-DMTE_REC_PLAIN_ARGS", os.path.join(csrc, "optim.hip"), os.path.join(TESTS, "optim_launch_driver.cpp")]
     else:
         cmd += [os.path.join(TESTS, "conv_launch_driver.cpp")]
     cmd += ["-o", exe]
@@ -823,10 +828,125 @@ def wgrad_cases():
             add("wgrad", BF16, 8, 48, 160, c, n, k, shared=0, cus=cus, knobs=[(26, 0)])
     return out
 
+# ---- the optimizer family (--optim): the 16 launching entry points of optim.hip and its three work-buffer queries
+OPT_EDGE = 4 * 256 * 8192           # elements at which opt_grid reaches its cap of 8192 workgroups
+OPT_REAL = 76993280                 # about the real layout's size (a multiple of 64)
+OPT_NS = (0, 1, 3, 4, 5, 64, 1023, 1024, OPT_EDGE - 4, OPT_EDGE, OPT_EDGE + 4, OPT_REAL)
+OPT_NS_64 = (0, 64, 128, 960, 1024, 1088, OPT_EDGE - 64, OPT_EDGE, OPT_EDGE + 64, OPT_REAL)      # the SEG forms want n % 64 == 0
+STAT_CHUNK, STAT_CAP, STAT_MAX_T = 32768, 1024, 4096                    # csrc/optim_plan.hpp
+OPT_PTRS = {                                                             # the pointer arguments of each entry point, by the driver's names
+    "ema_update": "p b", "ema_update_dev": "p b scal ctl", "flat_swap": "p b", "grad_accumulate": "p b", "grad_norm_clip": "g work ctl",
+    "adamw_step": "p g m v", "adamw_step_dev": "p g m v hyper", "adamw_step_ctl_dev": "p g m v hyper ctl", "adamw_step_seg_dev": "p g m v hyper cls scales ctl",
+    "sgd_step": "p g buf", "sgd_step_dev": "p g buf hyper", "sgd_step_ctl_dev": "p g buf hyper ctl", "sgd_step_seg_dev": "p g buf hyper cls scales ctl",
+    "tensor_stats": "g p begin numel work out", "lamb_moments": "p g m v hyper begin numel table work trust sums ctl",
+    "lamb_apply": "p m v hyper begin numel table trust ctl"}
+OPT_PAIR = ("ema_update", "ema_update_dev", "flat_swap", "grad_accumulate")
+OPT_ADAM = ("adamw_step", "adamw_step_dev", "adamw_step_ctl_dev", "adamw_step_seg_dev")
+OPT_SGD = ("sgd_step", "sgd_step_dev", "sgd_step_ctl_dev", "sgd_step_seg_dev")
+OPT_CHUNK = ("tensor_stats", "lamb_moments", "lamb_apply")
+OPT_QUERIES = ("grad_norm_work_bytes", "tensor_stats_work_bytes", "lamb_work_bytes")
 
-def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False, patch=False, wgrad=False):
+
+def optim_case(entry, n=1024, T=2, wd="0.01", dec=1, mom="0.9", nest=0, damp="0", step=2, ncls=2, trust="10", norm="1", flag=None, err="-"):
+    """flag: None = the usual one (grad_accumulate: add; everything else: 1 -- with ctl, with p, skip_nonfinite)"""
+    flag = (0 if entry == "grad_accumulate" else 1) if flag is None else flag
+    return "%s %d %d %s %d %s %d %s %d %d %s %s %d %s" % (entry, n, T, wd, dec, mom, nest, damp, step, ncls, trust, norm, flag, err)
+
+
+def optim_cases():
+    out = []
+
+    def add(*a, **kw):
+        c = optim_case(*a, **kw)
+        if c not in out:
+            out.append(c)
+
+    # ---- every entry point over n: the tails, one workgroup and two, the grid cap's edge, the real size; n < 0
+    for entry in OPT_PTRS:
+        for n in (OPT_NS_64 if entry.endswith("_seg_dev") else OPT_NS) + (-1, -64):
+            add(entry, n)
+    # ---- every instance selector
+    for entry in OPT_ADAM:
+        for wd in ("0", "0.01"):
+            for dec in (0, 1):
+                add(entry, wd=wd, dec=dec)
+    for entry in OPT_SGD:
+        for mom, nest in (("0", 0), ("0.9", 0), ("0.9", 1)):
+            for wd in ("0", "0.01"):
+                add(entry, mom=mom, nest=nest, wd=wd)
+        add(entry, mom="0", err="null:buf")                                # without momentum `buf` may be null
+        add(entry, damp="0.5")
+        add(entry, step=1)
+    for entry in ("adamw_step_seg_dev", "sgd_step_seg_dev"):
+        for ncls in (1, 16):
+            for flag in (0, 1):
+                add(entry, ncls=ncls, flag=flag)
+    for entry in ("ema_update_dev", "tensor_stats", "grad_accumulate", "grad_norm_clip", "lamb_moments", "lamb_apply"):
+        for flag in (0, 1):
+            add(entry, flag=flag)
+    add("lamb_moments", trust="0")
+    add("lamb_moments", wd="0")
+    add("lamb_apply", wd="0")
+    add("grad_norm_clip", norm="inf")
+    # ---- the chunk launches: T, and n / STAT_CHUNK + T below, at and above STAT_CAP, and on both sides of the largest int
+    for entry in OPT_CHUNK:
+        for T in (1, 2, STAT_MAX_T):
+            for n in (1024, STAT_CHUNK * (STAT_CAP - 1 - T), STAT_CHUNK * (STAT_CAP - T), STAT_CHUNK * (STAT_CAP + 1 - T), STAT_CHUNK * (2 ** 31 - 1 - T),
+                      STAT_CHUNK * (2 ** 31 - T)):
+                if n > 0:
+                    add(entry, n, T)
+    # ---- every argument error, one case per rule (a pointer the entry point does not test is recorded too: it is launched)
+    for entry, ptrs in OPT_PTRS.items():
+        n = 1024
+        for name in ptrs.split():
+            add(entry, n, err="null:" + name)
+            add(entry, n, err="mis:" + name)
+        if entry in OPT_PAIR:
+            for n2 in (0, 4, 5, 1024):                                     # 16 bytes apart: disjoint up to four elements
+                add(entry, n2, err="eq")
+                add(entry, n2, err="overlap")
+        if entry in OPT_ADAM + OPT_SGD + ("lamb_moments", "lamb_apply"):
+            for wd in ("-1", "nan", "-0"):
+                add(entry, n, wd=wd)
+        if entry in OPT_ADAM[:1] + OPT_SGD[:1]:
+            for step in (0, -1):
+                add(entry, n, step=step)
+        if entry in OPT_SGD:
+            for mom in ("-1", "nan"):
+                add(entry, n, mom=mom)
+            add(entry, n, mom="0", nest=1)                                 # Nesterov without momentum
+            add(entry, n, nest=1, damp="0.5")                              # ... and with dampening (the host form's rule)
+        if entry.endswith("_seg_dev"):
+            for n2 in (1000, 1028):
+                add(entry, n2)
+            for ncls in (0, 17, -1):
+                add(entry, n, ncls=ncls)
+        if entry in OPT_CHUNK:
+            for T in (0, STAT_MAX_T + 1, -1):
+                add(entry, n, T)
+        if entry == "lamb_moments":
+            for trust in ("-1", "nan"):
+                add(entry, n, trust=trust)
+        if entry == "grad_norm_clip":
+            for norm in ("0", "nan", "-1"):
+                add(entry, n, norm=norm)
+    # ---- the three queries over the same n and T
+    for n in OPT_NS + (-1, STAT_CHUNK * (STAT_CAP - 2)):
+        add("grad_norm_work_bytes", n)
+        for T in (0, 1, 2, STAT_MAX_T, STAT_MAX_T + 1):
+            add("tensor_stats_work_bytes", n, T)
+            add("lamb_work_bytes", n, T)
+    for n in (256 * 4 * 255, 256 * 4 * 255 + 4, 256 * 4 * 256, 256 * 4 * 256 + 4):      # the norm grid's cap
+        add("grad_norm_work_bytes", n)
+        add("grad_norm_clip", n)
+    return out
+
+
+def record(csrc=CSRC, dev=True, extra=(), gn=False, p3=False, patch=False, wgrad=False, optim=False):
     with tempfile.TemporaryDirectory() as tmp:
-        cs = gn_cases() if gn else p3_cases() if p3 else patch_cases() if patch else wgrad_cases() if wgrad else cases()
+        cs = gn_cases() if gn else p3_cases() if p3 else patch_cases() if patch else wgrad_cases() if wgrad else optim_cases() if optim else cases()
+        if optim:                                                          # no knobs: one build, and a case's last word is its error, not a knob list
+            return run(build(tmp, dev, csrc, extra, optim=True), cs)
         return run(build(tmp, dev, csrc, extra, gn, p3, patch, wgrad), cs if dev else [c for c in cs if c.endswith(" -")])
 
 
@@ -846,10 +966,11 @@ if __name__ == "__main__":
     ap.add_argument("--p3", action="store_true", help="conv3d pack / unpack (pack3d.hip, tests/p3_launch_table.json)")
     ap.add_argument("--patch", action="store_true", help="LDS-patch convolution (conv_patch.hip, tests/patch_launch_table.json)")
     ap.add_argument("--wgrad", action="store_true", help="weight gradient (mte_conv2d_wgrad: conv_igemm.hip, conv_wgrad9.hip, tests/wgrad_launch_table.json)")
+    ap.add_argument("--optim", action="store_true", help="the optimizer family (optim.hip, tests/optim_launch_table.json)")
     a = ap.parse_args()
-    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3, patch=a.patch, wgrad=a.wgrad)
+    lines = record(a.csrc, dev=not a.product, gn=a.gn, p3=a.p3, patch=a.patch, wgrad=a.wgrad, optim=a.optim)
     for ln in lines:
         json.loads(ln)
-    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else PATCH_TABLE if a.patch else WGRAD_TABLE if a.wgrad else TABLE) if a.write else a.out, "w") as f:
+    with open((GN_TABLE if a.gn else P3_TABLE if a.p3 else PATCH_TABLE if a.patch else WGRAD_TABLE if a.wgrad else OPTIM_TABLE if a.optim else TABLE) if a.write else a.out, "w") as f:
         f.write("[\n" + ",\n".join(lines) + "\n]\n")
     print("%d cases" % len(lines))

@@ -1,14 +1,16 @@
 // Launch recorder for the host code that chooses kernels (tests/conv_launch_recorder.py): force-included in front of conv_igemm.hip / conv_igemm8.hip /
-// conv_wgrad9.hip / norm_act.hip / pack3d.hip / conv_patch.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync, hipGetLastError,
+// conv_wgrad9.hip / norm_act.hip / pack3d.hip / conv_patch.hip / optim.hip when they are compiled for the host alone.  hipLaunchKernelGGL, hipFuncSetAttribute, hipMemsetAsync, hipGetLastError,
 // hipGetDevice and hipDeviceGetAttribute (answered with the CU count the driver sets) are redefined, so no
 // call reaches the HIP runtime: every launch is appended to a text record instead -- the kernel with its template arguments, grid, block, dynamic LDS, the
-// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args, P3LArgs, PatchArgs, PatchWgradArgs, WgradArgs or Wgrad9Args argument the fields the host chose.  A clear (hipMemsetAsync, or the fill
+// large-LDS grant the kernel holds at that moment, and for a ConvArgs, GnArgs, P3Args, P3LArgs, PatchArgs, PatchWgradArgs, WgradArgs or Wgrad9Args argument (and the optimizer family's NormArgs, StatArgs, LambArgs, SegArgs and step scalars) the fields the host chose.  A clear (hipMemsetAsync, or the fill
 // kernels of mte_memset_async in common.hpp) is a line of its own: which buffer and how many bytes.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cxxabi.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <stdlib.h>
+#include <initializer_list>
 #include <map>
 #include <typeinfo>
 #include <string>
@@ -44,6 +46,7 @@ template <auto K> std::string kernel_name() {
     return s;
 }
 
+inline std::string& plain() { static std::string s; return s; }      // the plain (non-struct) arguments of the launch being recorded
 inline void field(const char* name, long v, long dflt) { if (v != dflt) log() += std::string(",\"") + name + "\":" + std::to_string(v); }
 
 template <typename A, typename = void> struct is_gn_args : std::false_type {};
@@ -60,6 +63,21 @@ template <typename A, typename = void> struct is_wgrad_args : std::false_type {}
 template <typename A> struct is_wgrad_args<A, std::void_t<decltype(A::blocks_per_split), decltype(A::tiles_n), decltype(A::part_stride)>> : std::true_type {};
 template <typename A, typename = void> struct is_wgrad9_args : std::false_type {};         // Wgrad9Args: the nine-tap weight gradient
 template <typename A> struct is_wgrad9_args<A, std::void_t<decltype(A::units_per_split), decltype(A::base), decltype(A::part_stride)>> : std::true_type {};
+// the optimizer family (optim.hip): NormArgs, StatArgs, LambArgs, SegArgs, and the by-value step scalars with or without their ctl pointer
+template <typename A, typename = void> struct is_norm_args : std::false_type {};
+template <typename A> struct is_norm_args<A, std::void_t<decltype(A::max_norm), decltype(A::skip_nonfinite), decltype(A::records)>> : std::true_type {};
+template <typename A, typename = void> struct is_stat_args : std::false_type {};
+template <typename A> struct is_stat_args<A, std::void_t<decltype(A::tickets), decltype(A::max_chunks), decltype(A::out)>> : std::true_type {};
+template <typename A, typename = void> struct is_lamb_args : std::false_type {};
+template <typename A> struct is_lamb_args<A, std::void_t<decltype(A::max_trust), decltype(A::trust), decltype(A::sums)>> : std::true_type {};
+template <typename A, typename = void> struct is_seg_args : std::false_type {};
+template <typename A> struct is_seg_args<A, std::void_t<decltype(A::cls), decltype(A::scales), decltype(A::n_classes)>> : std::true_type {};
+template <typename A, typename = void> struct is_adam_scalars : std::false_type {};
+template <typename A> struct is_adam_scalars<A, std::void_t<decltype(A::bc1), decltype(A::bc2s), decltype(A::gscale)>> : std::true_type {};
+template <typename A, typename = void> struct is_sgd_scalars : std::false_type {};
+template <typename A> struct is_sgd_scalars<A, std::void_t<decltype(A::mu_eff), decltype(A::omd_eff), decltype(A::gscale)>> : std::true_type {};
+template <typename A, typename = void> struct has_ctl : std::false_type {};
+template <typename A> struct has_ctl<A, std::void_t<decltype(A::ctl)>> : std::true_type {};
 // compute units the device query answers (the weight-gradient driver sets it per case): no case depends on whether the machine has a GPU
 inline int& cus() { static int n = 256; return n; }
 inline hipError_t get_device(int* dev) { *dev = 0; return hipSuccess; }
@@ -68,6 +86,27 @@ inline hipError_t device_attribute(int* v, hipDeviceAttribute_t what, int) {    
     *v = cus();
     return hipSuccess;
 }
+
+// a pointer as the driver's buffer name (+ offset), "0" when null
+inline std::string ptr_name(const void* p) {
+    if (!p) return "0";
+    auto it = buffers().upper_bound((uintptr_t)p);
+    if (it == buffers().begin()) return std::to_string((uintptr_t)p);
+    --it;
+    return (uintptr_t)p == it->first ? it->second : it->second + "+" + std::to_string((uintptr_t)p - it->first);
+}
+inline void ptrs(const char* name, std::initializer_list<const void*> ps) {
+    std::string s;
+    for (const void* p : ps) s += (s.empty() ? "" : " ") + ptr_name(p);
+    log() += std::string(",\"") + name + "\":\"" + s + "\"";
+}
+inline void floats(const char* name, std::initializer_list<float> vs) {      // %.9g: every float32 has its own text
+    std::string s;
+    char b[32];
+    for (float v : vs) { snprintf(b, sizeof b, "%.9g", (double)v); s += (s.empty() ? "" : " ") + std::string(b); }
+    log() += std::string(",\"") + name + "\":\"" + s + "\"";
+}
+template <typename A> void adam_scalars(const A& s) { floats("adam", {s.lr, s.bc1, s.bc2s, s.b1, s.b2, s.eps, s.gscale, s.wd}); }
 
 // (to keep the table small a field is left out where it has its usual value: grid y, z = 1, granted = 0, splits = 1, the other fields 0, a pointer null)
 template <typename A> void arg_fields(const A& a) {
@@ -99,7 +138,30 @@ template <typename A> void arg_fields(const A& a) {
     } else if constexpr (is_wgrad9_args<A>::value) {
         field("tiles_c", a.tiles_c, 0); field("base", a.base, 0); field("units", a.units, 0); field("units_per_split", a.units_per_split, 0);
         field("part_stride", a.part_stride, 0);
+    } else if constexpr (is_norm_args<A>::value) {
+        field("n", a.n, 0); floats("norm", {a.gscale, a.max_norm}); field("skip_nonfinite", a.skip_nonfinite, 0); field("fences", a.fences, 0);
+        ptrs("ptrs", {a.g, a.sum, a.ticket, a.records, a.ctl});
+    } else if constexpr (is_stat_args<A>::value) {
+        field("n", a.n, 0); field("T", a.T, 0); field("fences", a.fences, 0); field("max_chunks", a.max_chunks, 0);
+        ptrs("ptrs", {a.g, a.p, a.begin, a.numel, a.tickets, a.records, a.out});
+    } else if constexpr (is_lamb_args<A>::value) {
+        field("n", a.n, 0); field("T", a.T, 0); field("fences", a.fences, 0); field("max_chunks", a.max_chunks, 0);
+        adam_scalars(a.s); floats("max_trust", {a.max_trust});
+        ptrs("ptrs", {a.p, a.g, a.m, a.v, a.hyper, a.ctl, a.begin, a.numel, a.table, a.tickets, a.records, a.trust, a.sums});
+    } else if constexpr (is_seg_args<A>::value) {
+        field("n_classes", a.n_classes, 0); ptrs("seg", {a.cls, a.scales, a.ctl});
+    } else if constexpr (is_adam_scalars<A>::value) {
+        adam_scalars(a);
+        if constexpr (has_ctl<A>::value) ptrs("ctl", {a.ctl});
+    } else if constexpr (is_sgd_scalars<A>::value) {
+        floats("sgd", {a.lr, a.mu_eff, a.omd_eff, a.mu, a.gscale, a.wd});
+        if constexpr (has_ctl<A>::value) ptrs("ctl", {a.ctl});
     }
+#ifdef MTE_REC_PLAIN_ARGS                                                   // (the optimizer recorder) the kernels' plain arguments too, in order: "a":"p g m v 1024 hyper"
+    else if constexpr (std::is_pointer_v<A>) plain() += (plain().empty() ? "" : " ") + ptr_name((const void*)a);
+    else if constexpr (std::is_integral_v<A>) plain() += (plain().empty() ? "" : " ") + std::to_string((long)a);
+    else if constexpr (std::is_floating_point_v<A>) { char b[32]; snprintf(b, sizeof b, "%.9g", (double)a); plain() += (plain().empty() ? "" : " ") + std::string(b); }
+#endif
 }
 
 inline hipError_t clear(const void* p, size_t bytes) {
@@ -122,7 +184,9 @@ template <auto K, typename... A> void launch(dim3 g, dim3 b, size_t lds, hipStre
     field("grid_y", g.y, 1); field("grid_z", g.z, 1);
     field("block", b.x, -1); field("block_y", b.y, 1); field("block_z", b.z, 1);
     field("lds", (long)lds, -1); field("granted", it == granted().end() ? 0 : it->second, 0);
+    plain().clear();
     (arg_fields(args), ...);
+    if (!plain().empty()) log() += ",\"a\":\"" + plain() + "\"";
     log() += "}";
 }
 inline hipError_t set_attribute(const void* k, hipFuncAttribute, int v) { granted()[k] = v; return hipSuccess; }

@@ -7,7 +7,8 @@ The layout is FlatParameters' of PackNetSAN01 '1A' (218 tensors, each aligned to
 configs/train_packnet_san_kitti_with_edges_finetune.yaml (four classes).  The launches, alternating in one process as
 tools/optimizer_timing.py runs them (every round times each once, `inner` back-to-back launches between two events, after a warm-up
 round): mte_adamw_step_dev and mte_adamw_step_seg_dev (AdamW, 28 B per parameter), mte_sgd_step_dev and mte_sgd_step_seg_dev (SGD with
-momentum, 20 B), mte_grad_norm_clip (4 B) and mte_tensor_stats without and with the weights (4 B and 8 B per parameter read).
+momentum, 20 B; the SEG form with Nesterov's look-ahead too, and both without momentum, 12 B: the three momentum instances of the SEG
+kernel), mte_grad_norm_clip (4 B) and mte_tensor_stats without and with the weights (4 B and 8 B per parameter read).
 Expectations, not bars: the class map adds one byte per 64 elements, so a SEG launch should sit inside its plain launch's own min-max
 spread plus 1 %; the statistics launch should be near the norm launch's rate per byte read.  Needs the GPU; there is no fallback."""
 import argparse
@@ -69,6 +70,7 @@ def main():
     st = K._stream()
     adam = (p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr(), n, adam_hyper.data_ptr(), 0.9, 0.999, 1e-8)
     sgd = (p.data_ptr(), g.data_ptr(), buf.data_ptr(), n, sgd_hyper.data_ptr(), 0.9)
+    sgd0 = sgd[:5] + (0.0,)                                  # momentum 0: `buf` is neither read nor written
     cls = torch.tensor(blocks, dtype=torch.uint8).cuda()
     scales = torch.tensor([x for pair in classes for x in pair], dtype=torch.float32).cuda()
     seg = (cls.data_ptr(), scales.data_ptr(), len(classes), None)
@@ -87,11 +89,15 @@ def main():
         ('adamw, SEG form (4 classes)', 28, lambda: K.lib.mte_adamw_step_seg_dev(*adam, 0.01, 1, 1.0, *seg, st)),
         ('sgd momentum (mte_sgd_step_dev)', 20, lambda: K.lib.mte_sgd_step_dev(*sgd, 0.01, 0, 1.0, st)),
         ('sgd momentum, SEG form (4 classes)', 20, lambda: K.lib.mte_sgd_step_seg_dev(*sgd, 0.01, 0, 1.0, *seg, st)),
+        ('sgd Nesterov, SEG form (4 classes)', 20, lambda: K.lib.mte_sgd_step_seg_dev(*sgd, 0.01, 1, 1.0, *seg, st)),
+        ('sgd plain (mte_sgd_step_dev, momentum 0)', 12, lambda: K.lib.mte_sgd_step_dev(*sgd0, 0.01, 0, 1.0, st)),
+        ('sgd plain, SEG form (4 classes)', 12, lambda: K.lib.mte_sgd_step_seg_dev(*sgd0, 0.01, 0, 1.0, *seg, st)),
         ('grad norm + clip coefficient', 4, lambda: K.lib.mte_grad_norm_clip(g.data_ptr(), n, 1.0, 1.0, 1, norm_work.data_ptr(), norm_ctl.data_ptr(), st)),
         ('tensor stats, gradient only', 4, lambda: stats(False)),
         ('tensor stats, gradient and weights', 8, lambda: stats(True)),
     ]
-    plain_of = {'adamw, SEG form (4 classes)': 'adamw (mte_adamw_step_dev)', 'sgd momentum, SEG form (4 classes)': 'sgd momentum (mte_sgd_step_dev)'}
+    plain_of = {'adamw, SEG form (4 classes)': 'adamw (mte_adamw_step_dev)', 'sgd momentum, SEG form (4 classes)': 'sgd momentum (mte_sgd_step_dev)',
+                'sgd Nesterov, SEG form (4 classes)': 'sgd momentum (mte_sgd_step_dev)', 'sgd plain, SEG form (4 classes)': 'sgd plain (mte_sgd_step_dev, momentum 0)'}
     times = {name: [] for name, _, _ in launches}
     for rnd in range(-1, args.rounds):                       # round -1: warm-up of every launch
         for name, _, fn in launches:
