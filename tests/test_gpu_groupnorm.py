@@ -9,24 +9,11 @@ with and without the second input / the fused conv-bias gradient, in fp32 mode (
 Shapes include the real ones: 512 channels at 24x80 (conv5 blocks), 256 at 48x160 (forward slab only), 512 at 12x40."""
 import pytest
 import torch
-import torch.nn.functional as F
 
 from conftest import kernel_variant, rel_err
+from gn_ref import _reference, _tail_reference
 
 pytestmark = pytest.mark.gpu
-
-
-def _reference(y1, y2, scale2, gamma, beta, dz):
-    y1 = y1.double().requires_grad_(True)
-    gamma, beta = gamma.double().requires_grad_(True), beta.double().requires_grad_(True)
-    v = y1
-    if y2 is not None:
-        y2 = y2.double().requires_grad_(True)
-        v = y1 + y2 * scale2.double()[:, :, None, None]
-    z = F.elu(F.group_norm(v, 16, gamma, beta, eps=1e-5))
-    z.backward(dz.double())
-    # bias gradient of the conv in front of the norm: column sums of d1 -- with a second input, of d2 (the shortcut conv's bias)
-    return (z.detach(), y1.grad, None if y2 is None else y2.grad, gamma.grad, beta.grad, (y1.grad if y2 is None else y2.grad).sum(dim=(0, 2, 3)))
 
 
 def _run(dtype, B, C, H, W, has2, slab):
@@ -143,17 +130,6 @@ def test_cluster_route_is_taken_and_is_bit_reproducible():
 
 
 # ---- round 5: the residual block's tail in two launches (mte_gn_tail_fwd) and its backward (mte_gn_elu_bwd with a scaled second output)
-def _tail_reference(y1, s, scale, g1, b1, gt, bt, dz):
-    y1, s = y1.double().requires_grad_(True), s.double().requires_grad_(True)
-    ps = [p.double().requires_grad_(True) for p in (g1, b1, gt, bt)]
-    a = F.elu(F.group_norm(y1, 16, ps[0], ps[1], eps=1e-5))
-    t = a + (s * scale.double()[:, :, None, None] if scale is not None else s)
-    z = F.elu(F.group_norm(t, 16, ps[2], ps[3], eps=1e-5))
-    z.backward(dz.double())
-    return {"t": t.detach(), "z": z.detach(), "dy1": y1.grad, "ds": s.grad, "dg1": ps[0].grad, "db1": ps[1].grad, "dgt": ps[2].grad, "dbt": ps[3].grad,
-            "dbias_s": s.grad.sum(dim=(0, 2, 3)), "dbias1": y1.grad.sum(dim=(0, 2, 3))}
-
-
 def _tail_run(K, y1, s, scale, g1, b1, gt, bt, dz):
     B, C, H, W = y1.shape
     dt_ = K._dt(y1)
