@@ -775,6 +775,26 @@ int mte_lidar_scatter(int H, int W, int n, const unsigned char* keep, int n_keep
 int mte_lidar_project(const double* points, int N, const double* K, const float* depth_map, float* out, int H, int W, int* winner_ws,
                       mte_stream_t stream);
 
+/* ---- the perturbation above for a whole batch in a fixed number of launches and without a host read (datasets/lidar_prep.py::
+ * perturb_batch, called by datasets/prefetch.py::DeviceStage; csrc/lidar_prep.hip).  index -> perturb -> scatter of mte_lidar_index /
+ * mte_lidar_perturb / mte_lidar_scatter, the same kernel bodies with the sample in blockIdx.y, over lidar float32 [B,H,W] into out float32
+ * [B,H,W] (every element written).  The host has computed both counts of every map beforehand (lidar_prep.py::resized_cells,
+ * count_survivors) and has sized the draws with them.
+ * arena (arena_bytes bytes, on the device) holds the draws; table: B rows of MTE_LIDAR_BATCH_ROW_WORDS 64-bit integers
+ *   (n, n', bits of the double scale_d0, add_i_off, add_j_off, add_d_off, keep_off, 0): byte offsets into the arena of float64 [n] x 3
+ *   (8-byte aligned) and uint8 [n'].  table_host and table_dev hold the SAME rows: the host copy is checked before anything is launched
+ *   (0 <= n' <= n <= H*W, every array inside the arena; MTE_ERR_ARG otherwise), the kernels read the device copy.
+ * Every loop runs to min(the table's count, the device's own count), so a table whose counts are wrong gives a wrong map, never an access
+ *   outside the draws or the workspace; status int [B,4] = (n of the table, n of the device, n' of the table, n' of the device) per sample is
+ *   written by the last launch for the host to compare afterwards.
+ * work: mte_batch_lidar_perturb_work_bytes(B, H, W) bytes (0 for an unsupported shape; B <= 65535), 8-byte aligned, content on entry ignored;
+ *   one private area per sample.  Nine launches whatever B is; double arithmetic, integer atomics only, no kernel waits on another
+ *   workgroup: bit-reproducible. */
+#define MTE_LIDAR_BATCH_ROW_WORDS 8
+long mte_batch_lidar_perturb_work_bytes(int B, int H, int W);
+int mte_batch_lidar_perturb(const float* lidar, int B, int H, int W, const unsigned char* arena, long arena_bytes, const long* table_host,
+                            const long* table_dev, float* out, void* work, int* status, mte_stream_t stream);
+
 /* ---- depth visualisation and ordinal error of the inference side (utils/depth.py:67-101 viz_inv_depth; infer_edges.py:355-366 the log
  * colouring; utils/d3r.py), csrc/depth_viz.hip.  Every result is an integer or a copy of an input value: no floating-point atomics, results
  * are bit-equal run to run.  Inputs are FINITE float32 (a NaN has no place in the order; it is not looked for).

@@ -25,7 +25,7 @@ RETURNS = {}
 # entry points that return a value (capability / size queries) instead of an error code
 QUERIES = ("mte_conv2d_patch_supported", "mte_conv2d_stem_supported", "mte_conv2d_patch_wgrad_supported", "mte_conv2d_wgrad_nine_tap", "mte_conv2d_patch_fwd_gn_elems", "mte_conv2d_patch_pack_elems", "mte_depth_metrics_workspace_bytes",
            "mte_chamfer_workspace_bytes", "mte_edge_match_workspace_bytes", "mte_edge_loss_sums_elems", "mte_gn_fwd_is_single_pass", "mte_gn_fwd_is_single_pass_b",
-           "mte_edge_loss_work_elems", "mte_edge_loss_pair_work_elems", "mte_edge_loss_kind_work_elems", "mte_supervised_loss_work_elems", "mte_rank1_conv_bwd_records_elems", "mte_conv2d_patch_fwd_rank1_ok", "mte_gn_stats_elems", "mte_device_error_poll", "mte_invdepth_bwd_weight_workspace_elems", "mte_sparse_site_list_workspace_elems", "mte_image_resample_work_bytes", "mte_lidar_perturb_work_bytes", "mte_order_stats_work_bytes",
+           "mte_edge_loss_work_elems", "mte_edge_loss_pair_work_elems", "mte_edge_loss_kind_work_elems", "mte_supervised_loss_work_elems", "mte_rank1_conv_bwd_records_elems", "mte_conv2d_patch_fwd_rank1_ok", "mte_gn_stats_elems", "mte_device_error_poll", "mte_invdepth_bwd_weight_workspace_elems", "mte_sparse_site_list_workspace_elems", "mte_image_resample_work_bytes", "mte_lidar_perturb_work_bytes", "mte_batch_lidar_perturb_work_bytes", "mte_order_stats_work_bytes",
            "mte_pack_ring_work_elems", "mte_pack_border_scatter_work_elems", "mte_pack_border_class_sums_elems", "mte_grad_norm_work_bytes",
            "mte_pack_border_gemm_ws_elems", "mte_tensor_stats_work_bytes", "mte_lamb_work_bytes")
 

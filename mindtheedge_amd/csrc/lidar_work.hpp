@@ -17,7 +17,7 @@ struct LpWork {                                           // the caller's worksp
 __host__ __device__ inline long lp_blocks(long hw) { return (hw + LP_CHUNK - 1) / LP_CHUNK; }
 __host__ __device__ inline long lp_round4(long v) { return (v + 3) & ~3L; }
 inline long lp_work_bytes(long hw) { return 4 * (LP_HEAD + lp_round4(lp_blocks(hw)) + 4 * lp_round4(hw)) + 8 * hw; }
-inline LpWork lp_carve(void* work, long hw) {
+__host__ __device__ inline LpWork lp_carve(void* work, long hw) {
     LpWork w;
     w.head = (int*)work;
     w.minkey = (long long*)(w.head + 2);

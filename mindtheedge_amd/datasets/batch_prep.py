@@ -2,7 +2,8 @@
 
   * ``decode_train_record``   host stage: the files of one split record as numpy arrays, nothing else.  It runs on worker threads and
                               touches neither ``torch.cuda`` nor the kernel library: all device work is the consumer thread's.
-  * ``plan_targets``          the descriptor rows (csrc/batch_prep.hip) and the output layout of a batch's depth / edge / normal targets
+                              With the LiDAR column it also reads that file, raw, and counts the returns of the resized map.
+  * ``plan_targets``          the descriptor rows (csrc/batch_prep.hip) and the output layout of a batch's depth / LiDAR / edge / normal targets
   * ``HostArena`` / ``pack_arena``   the raw arrays of a batch and the descriptor table in ONE buffer at 16-byte-aligned offsets, so that
                               a batch is one upload
   * ``prepare_targets``       device stage: ``mte_batch_prep`` over the uploaded arena -> {'depth', 'edge', .., 'normal', ..} float32
@@ -42,10 +43,14 @@ def _read_depth_raw(path):
     return depth
 
 
-def decode_train_record(rec, root='', with_lidar=False):
+def decode_train_record(rec, root='', with_lidar=False, lidar_raw=True, crop_borders=(), shape=None):
     """One record of the split file (kitti_edges.parse_split_line) -> {'rgb': uint8 [h,w,3], 'depth': uint16 [h,w] (.png) / float32 (.npy) /
-    None, 'edge': [uint8 [h_s,w_s] per scale], 'normal': [...]}.  with_lidar adds 'lidar_path' (resolved, not read: the LiDAR column is
-    read at hand-over by the per-sample functions).  Pure file decoding; safe on any thread."""
+    None, 'edge': [uint8 [h_s,w_s] per scale], 'normal': [...]}.  with_lidar adds 'lidar_path' (resolved) and 'lidar': the file's map, raw
+    (lidar_prep.read_lidar_raw: uint16 for a 16-bit .png, float32 for .npy / .npz) -- or None for a velodyne .bin, whose batch goes through
+    the per-sample functions at hand-over (lidar_batchable), and with lidar_raw=False (the per-sample path for every batch).  With shape
+    (the dataset's (H, W); crop_borders its crop_train_borders) it also adds 'lidar_cells': the returns of the cropped and resized map
+    (lidar_prep.resized_cells), so that the count the draws depend on is known before the batch is handed over.  Pure file decoding and
+    numpy; safe on any thread."""
     from PIL import Image
     from .kitti_edges import _read_gray_u8, multiscale_paths
 
@@ -60,7 +65,26 @@ def decode_train_record(rec, root='', with_lidar=False):
             out[name] = [np.ascontiguousarray(_read_gray_u8(q).astype(np.uint8)) for q in multiscale_paths(p(rec[name]))]
     if with_lidar:
         out['lidar_path'] = p(rec['lidar']) if rec.get('lidar') else None
+        out['lidar'] = out['lidar_cells'] = None
+        if out['lidar_path'] and lidar_raw:
+            from . import lidar_prep as lp
+            out['lidar'] = lp.read_lidar_raw(out['lidar_path'])
+            if out['lidar'] is not None and shape is not None:
+                out['lidar_cells'] = lp.resized_cells(out['lidar'], lidar_window(out, crop_borders), shape)
     return out
+
+
+def lidar_window(smp, crop_borders):
+    """the crop window of a sample's LiDAR map: crop_train_borders are resolved against the frame, as for every other map of the sample"""
+    from .image_prep import parse_crop_borders
+    borders = parse_crop_borders(crop_borders, smp['rgb'].shape[:2]) if crop_borders else None
+    return crop_window(borders, *smp['lidar'].shape)
+
+
+def lidar_batchable(samples):
+    """True where the LiDAR column of this batch goes through the batched pass: every sample carries a decoded map.  One velodyne .bin
+    (its return count depends on the device projection) sends the whole batch through the per-sample functions."""
+    return all(s.get('lidar') is not None for s in samples)
 
 
 def crop_window(borders, h, w):
@@ -74,7 +98,7 @@ def crop_window(borders, h, w):
     return x0, y0, y1 - y0, x1 - x0
 
 
-def plan_targets(samples, borders, shape):
+def plan_targets(samples, borders, shape, lidar=False):
     """samples: decode_train_record results of one batch; borders: per sample (left, top, right, bottom) or None; shape: (H, W).
     -> (arrays, rows, keys, fallbacks, winner_elems, out_elems):
       arrays        the source maps, in row order (the arena packs them)
@@ -82,13 +106,18 @@ def plan_targets(samples, borders, shape):
       keys          [(key, (H_s, W_s), first element in the output arena)] in the order of the collated sample; every key is
                     [B,1,H_s,W_s]; preserve-resized keys come first in the arena (their winner words share the offsets)
       fallbacks     [(key, b, index into arrays, crop window)]: normal maps that are not at their target size (mte_resize_linear path)
-    Every sample of a batch must carry the same maps (as kitti_edges.collate requires)."""
+    lidar: also lay out the decoded LiDAR maps (lidar_batchable) as the key 'lidar' behind 'depth': sparse rows with the scale-0 crop window,
+    like the depth map.  Every sample of a batch must carry the same maps (as kitti_edges.collate requires)."""
     H, W = int(shape[0]), int(shape[1])
     B = len(samples)
     first = samples[0]
     layout = []                                                          # (key, kind group, tgt)
     if first['depth'] is not None:
         layout.append(('depth', 'depth', 0, (H, W)))
+    if lidar:
+        if not lidar_batchable(samples):
+            raise KeyError("the LiDAR maps of this batch are not all decoded: it takes the per-sample path")
+        layout.append(('lidar', 'lidar', 0, (H, W)))
     for name in ('edge', 'normal'):
         for s in range(len(first[name])):
             layout.append((scale_key(name, s), name, s, (int(H / (2 ** s)), int(W / (2 ** s)))))
@@ -107,12 +136,12 @@ def plan_targets(samples, borders, shape):
     arrays, rows, fallbacks = [], [], []
     for key, name, s, tgt in layout:
         for b, smp in enumerate(samples):
-            a = smp['depth'] if name == 'depth' else smp[name][s]
+            a = smp[name] if name in ('depth', 'lidar') else smp[name][s]
             if a.ndim != 2:
                 raise ValueError("'{}' of sample {} is a {} array, expected [h,w]".format(key, b, a.shape))
             h, w = a.shape
             x0, y0, ch, cw = crop_window(borders[b] if s == 0 else None, h, w)      # crop_sample crops scale 0 only
-            if name == 'depth':
+            if name in ('depth', 'lidar'):
                 kind = SPARSE_U16 if a.dtype == np.uint16 else SPARSE_F32
             else:
                 kind = EDGE_U8 if name == 'edge' else NORMAL_U8
